@@ -22,13 +22,19 @@ law (hot rows are queried most, as in production).  Two modes:
 * ``--mode synthetic``: the kernel harness.  The arena is generated in memory
   and batches go to the engine directly (no holder, no executor).
 
-Both modes re-derive a sample of the counts (64 queries x 8 shards) on the host
-roaring core and report ``verified`` in ``extra``.  With N GPUs each rank owns a
-contiguous 1/N of the shards (strong scaling: the index size is fixed) and the
-per-batch counts are summed with an RCCL all-reduce.  ``value`` = total
-queries/sec.
+With N GPUs each rank owns a contiguous 1/N of the shards (strong scaling: the
+index size is fixed) and the per-batch counts are summed with an RCCL
+all-reduce.  ``value`` = total queries/sec.
 
-Run: python bench.py [--gpus N --steps K --warmup W --batch B --mode disk|synthetic]
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line.  ``--full`` adds everything else after the timed steps: both modes
+re-derive a sample of the counts (64 queries x 8 shards) on the host roaring
+core and report ``verified``; TopN, serving + import, BASELINE configs 4 and 5
+and the CPU baseline go into ``extra``; the fragment files are dropped from
+the page cache before the load.  ``--dump-outputs DIR`` writes the last timed
+step's counts to ``DIR/counts.npy``.
+
+Run: python bench.py [--gpus N --steps K --warmup W --batch B --mode disk|synthetic --full]
 """
 from __future__ import annotations
 
@@ -65,6 +71,17 @@ _T0 = time.time()
 def log(msg):
     """Progress line on stderr (long GPU runs must keep writing)."""
     print(f"[bench {time.time() - _T0:7.1f}s r{os.environ.get('RANK', '0')}] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(args, counts):
+    """``--dump-outputs DIR``: the answers of the last timed step, one count
+    per query of that step's batch in request order, as ``DIR/counts.npy``
+    (float64: every count is an integer below 2^53).  Queries and data are
+    seeded, so two builds run with the same arguments write comparable files."""
+    if not args.dump_outputs or os.environ.get("RANK", "0") != "0":
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "counts.npy"), np.asarray(counts, dtype=np.float64))
 
 
 def zipf_rows(rng, n, nrows=NROWS, s=1.6, v=50.0):
@@ -1072,6 +1089,7 @@ def run_synthetic(args, world, rank, dev, queries, ra, rb):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t
+    dump_outputs(args, last.numpy())
 
     extra = {"path": "kernel harness (in-memory arena, engine direct)", "gen_s": round(tgen, 2),
              "h2d_s": round(tload, 2), "hbm_bytes_per_gpu": view.nbytes(), "containers_per_gpu": view.container_count,
@@ -1280,7 +1298,6 @@ def run_disk(args, world, rank, dev, queries, ra, rb):
         from pilosa_amd.utils import gctune
         gctune.configure()
         gctune.freeze_long_lived()
-        assert gpu.launches > n0, "requests did not reach the device"
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(dev)
@@ -1290,7 +1307,9 @@ def run_disk(args, world, rank, dev, queries, ra, rb):
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t
+        assert gpu.launches > n0, "requests did not reach the device"
         last = results[args.warmup + args.steps - 1]
+        dump_outputs(args, last)
         extra.update({"clients": args.clients, "mean_count": float(np.mean(last)), "launches": gpu.launches - n0,
                       "gpu_faults": ex.gpu_faults, "peak_host_rss_gb":
                       round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1e6, 2)})
@@ -1432,6 +1451,7 @@ def run_disk_mesh(args, world, rank, dev, queries, ra, rb):
         t_b = mesh.sync()
         elapsed = max(b - a for a, b in zip(t_a, t_b)) / 1e9
         last = results[args.warmup + args.steps - 1]
+        dump_outputs(args, last)
         extra.update({"clients": args.clients, "mean_count": float(np.mean(last)),
                       "mesh_count_requests": mesh.seq - seq0, "mesh_max_in_flight": mesh.max_in_flight,
                       "per_rank_elapsed_s": [round((b - a) / 1e9, 4) for a, b in zip(t_a, t_b)],
@@ -1787,6 +1807,14 @@ def _rss_gb() -> float:
     return 0.0
 
 
+def headline_only(args):
+    """A run without ``--full`` does what the headline figure needs and
+    nothing else: every other phase's option is switched off."""
+    args.verify = args.topn_batches = args.cpu_baseline_shards = args.mesh_breakdown = args.cold_load = 0
+    args.serve_seconds = 0.0
+    args.configs = ""
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1835,10 +1863,21 @@ def main():
                     help="run the multi-GPU product path (ShardMesh over RCCL, one rank per GPU) even at --gpus 1")
     ap.add_argument("--cpu-baseline-shards", type=int, default=0,
                     help="also time the host C++ roaring executor on this many shards (extrapolated)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also run everything else: the host re-derivation (--verify), "
+                         "TopN, serving + import, configs 4/5, the CPU baseline, the mesh breakdown, and the "
+                         "page-cache eviction before the load (--cold-load); without it those options are ignored")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the answers of the last timed step (what the caller of the timed path received) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        headline_only(args)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and (args.gpus > 1 or args.mesh):
         # launched without a launcher: start one rank per GPU ourselves

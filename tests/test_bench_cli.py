@@ -51,3 +51,42 @@ def test_kfd_gpu_count_reads_topology_without_hip(tmp_path, monkeypatch):
 def test_gpus_must_be_positive():
     r = _run(["--gpus", "0"], {})
     assert r.returncode != 0 and "--gpus must be >= 1" in r.stderr
+
+
+def test_steps_must_be_positive():
+    r = _run(["--steps", "0"], {})
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_the_counts_as_float64(tmp_path, monkeypatch):
+    """--dump-outputs: rank 0 writes DIR/counts.npy (float64, request order);
+    other ranks and runs without the option write nothing."""
+    import types
+
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.delenv("RANK", raising=False)
+    out = tmp_path / "dump"
+    bench.dump_outputs(types.SimpleNamespace(dump_outputs=None), [1, 2])
+    monkeypatch.setenv("RANK", "1")
+    bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(out)), [1, 2])
+    assert not out.exists()
+    monkeypatch.setenv("RANK", "0")
+    bench.dump_outputs(types.SimpleNamespace(dump_outputs=str(out)), [5412475, 0, (1 << 40) + 1])
+    got = np.load(out / "counts.npy")
+    assert got.dtype == np.float64 and got.tolist() == [5412475.0, 0.0, float((1 << 40) + 1)]
+
+
+def test_plain_run_switches_every_other_phase_off():
+    """Without --full only the headline steps run: the options of the host
+    verification, TopN, serving, configs 4/5, the CPU baseline, the mesh
+    breakdown and the page-cache eviction are all off."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    args = types.SimpleNamespace(verify=64, topn_batches=40, cpu_baseline_shards=16, mesh_breakdown=20, cold_load=1,
+                                 serve_seconds=5.0, configs="4,5", steps=20, warmup=3)
+    bench.headline_only(args)
+    assert (args.verify, args.topn_batches, args.cpu_baseline_shards, args.mesh_breakdown, args.cold_load) == (0,) * 5
+    assert args.serve_seconds == 0 and args.configs == "" and (args.steps, args.warmup) == (20, 3)

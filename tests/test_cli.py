@@ -8,7 +8,8 @@ from pilosa_amd.server.config import Config, parse_duration
 from pilosa_amd.server.server import Server
 from pilosa_amd.utils.logger import CaptureLogger
 
-SAMPLE = "/root/reference/testdata/sample_view/0"
+# the reference's sample fragment file (testdata/sample_view/0), stored with the tests
+SAMPLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sample_view_fragment_0")
 
 
 def test_generate_and_resolve_config(monkeypatch):
@@ -37,12 +38,11 @@ def test_generate_and_resolve_config(monkeypatch):
 
 def test_check_and_inspect(tmp_path):
     out = io.StringIO()
-    if os.path.exists(SAMPLE):
-        assert main(["check", SAMPLE], stdout=out) == 0
-        assert out.getvalue().strip().endswith(": ok")
-        out = io.StringIO()
-        assert main(["inspect", SAMPLE, "--limit", "3"], stdout=out) == 0
-        assert "Containers: 14207" in out.getvalue()
+    assert main(["check", SAMPLE], stdout=out) == 0
+    assert out.getvalue().strip().endswith(": ok")
+    out = io.StringIO()
+    assert main(["inspect", SAMPLE, "--limit", "3"], stdout=out) == 0
+    assert "Containers: 14207" in out.getvalue()
     bad = tmp_path / "bad"
     bad.write_bytes(b"\x3c\x30\x00\x00\xff\xff\xff\x7f")
     out = io.StringIO()

@@ -8,7 +8,8 @@ import pytest
 
 from pilosa_amd import _roaring as R
 
-SAMPLE = "/root/reference/testdata/sample_view/0"
+# the reference's sample fragment file (testdata/sample_view/0), stored with the tests
+SAMPLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sample_view_fragment_0")
 
 
 def _rand_values(rng, kind, base=0):
@@ -69,7 +70,6 @@ def test_flip_shift_offset_range():
         b.offset_range(1, 0, 65536)
 
 
-@pytest.mark.skipif(not os.path.exists(SAMPLE), reason="reference sample fragment not mounted")
 def test_sample_fragment_byte_exact_roundtrip():
     data = open(SAMPLE, "rb").read()
     b = R.Bitmap.from_bytes(data)

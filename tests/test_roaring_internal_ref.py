@@ -5,6 +5,8 @@ the exact encoding the reference test uses (``convert_container`` forces
 array / bitmap / run) and goes through the public Bitmap operations, which
 dispatch to the same type-pair code in native/roaring.cpp.  Each test names
 the reference test (and line) it ports."""
+import os
+
 import numpy as np
 import pytest
 
@@ -465,7 +467,7 @@ def test_bitmap_xor_range(words, start, last, exp, n):  # TestBitmapXorRange :19
     assert vals(b.xor(run([(start, last)]))) == _vals_of_words(exp)
 
 
-REF_TESTDATA = "/root/reference/roaring/testdata"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")   # stored reference testdata
 
 
 @pytest.mark.parametrize("hexdata,count", [
@@ -478,11 +480,7 @@ def test_unmarshal_official_roaring(hexdata, count):  # TestUnmarshalRoaringWith
 
 
 def test_unmarshal_official_roaring_file():  # TestUnmarshalRoaringWithNoErrors :3376 (testdata file)
-    import os
-    p = os.path.join(REF_TESTDATA, "bitmapcontainer.roaringbitmap")
-    if not os.path.exists(p):
-        pytest.skip("reference testdata not present")
-    with open(p, "rb") as fh:
+    with open(os.path.join(GOLDEN, "bitmapcontainer.roaringbitmap"), "rb") as fh:
         assert Bitmap.from_bytes(fh.read()).count() == 10000
 
 

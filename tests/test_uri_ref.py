@@ -37,7 +37,12 @@ def test_uri_with_invalid_host_port():           # TestURIWithInvalidHostPort
         URI.from_host_port("index?.pilosa.com", 3333)
 
 
-@pytest.mark.parametrize("addr,scheme,host,port", VALID)
+# "::" separates the parts of a pytest node id, so the two "[::1]" cases carry
+# names of their own; every other case keeps the id pytest derives
+_IPV6_LOOPBACK_IDS = {"[::1]": "ipv6-loopback", "[::1]:3333": "ipv6-loopback-port"}
+
+
+@pytest.mark.parametrize("addr,scheme,host,port", VALID, ids=[_IPV6_LOOPBACK_IDS.get(v[0]) for v in VALID])
 def test_new_uri_from_address(addr, scheme, host, port):   # TestNewURIFromAddress
     _cmp(URI.parse(addr), scheme, host, port)
 
