@@ -326,6 +326,22 @@ void shadow_build(torch::Tensor view, int64_t S, torch::Tensor rows, torch::Tens
 }
 #endif  // PK_KBENCH
 
+// Bitmap twins of dense array rows (DeviceView.ensure_twin): the shadow build
+// kernel over another row list.
+void twin_build(torch::Tensor view, int64_t S, torch::Tensor rows, torch::Tensor twin) {
+  check_dev(rows, "rows");
+  check_dev(twin, "twin");
+  TORCH_CHECK(rows.scalar_type() == torch::kInt32, "rows must be int32[R]");
+  const int64_t R = rows.numel();
+  TORCH_CHECK(R >= 0 && R < (int64_t(1) << 20) && S > 0, "twin_build sizes");
+  TORCH_CHECK(twin.scalar_type() == torch::kInt64 && twin.numel() == R * S * 16 * 1024,
+              "twin must be int64[R*S*16*1024]");
+  pk::ViewDev v = viewdev_from(view);
+  pk::launch_shadow_build(v, int(S), rows.data_ptr<int32_t>(), int(R), reinterpret_cast<uint64_t*>(twin.data_ptr<int64_t>()),
+                          cur_stream(twin));
+  check_launch("twin_build");
+}
+
 void partial_sum_scatter(torch::Tensor partial, int64_t U, int64_t n, torch::Tensor ti, torch::Tensor out) {
   check_dev(partial, "partial");
   check_dev(ti, "ti");
@@ -343,7 +359,7 @@ void partial_sum_scatter(torch::Tensor partial, int64_t U, int64_t n, torch::Ten
 
 pk::ViewDev viewdev_from(const torch::Tensor& vd) {
   TORCH_CHECK(!vd.is_cuda() && vd.numel() * vd.element_size() == int64_t(sizeof(pk::ViewDev)),
-              "view must be a cpu tensor holding one ViewDev (64 bytes)");
+              "view must be a cpu tensor holding one ViewDev record");
   pk::ViewDev v;
   memcpy(&v, vd.data_ptr(), sizeof(v));
   return v;
@@ -976,6 +992,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "gfx950 HIP kernels for the bitmap index";
   m.attr("QUERYPROG_BYTES") = int(sizeof(pk::QueryProg));
   m.attr("VIEWDEV_BYTES") = int(sizeof(pk::ViewDev));
+  // pair-kernel variant ids of the bitmap twins / un-staging built into this module
+#ifdef PK_KBENCH
+  m.attr("PAIR_VARIANTS") = std::vector<int>{61, 62, 63, 64, 65};
+#else
+  m.attr("PAIR_VARIANTS") = std::vector<int>{63};
+#endif
   m.attr("MAXLEAF") = pk::MAXLEAF;
   m.attr("MAXPROG") = pk::MAXPROG;
   m.def("expr_count", &expr_count, "batched boolean-expression count over all local shards",
@@ -1011,6 +1033,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topn_cache_partial", &topn_cache_partial, "mesh cache-only TopN: one rank's membership + partial totals");
   m.def("topn_cache_select32", &topn_cache_select32, "mesh cache-only TopN: per-query top-n of the reduced buffer");
   m.def("row_counts_sum", &row_counts_sum, "ids= re-count without src: per id the sum of shard row counts >= threshold");
+  m.def("twin_build", &twin_build, "bitmap twins of dense array rows for the pair kernels");
   m.def("keymask_build", &keymask_build, "key-presence mask of every (shard, row) of a view");
   m.def("topn_hot_meta", &topn_hot_meta, "key-j container of every hot cache rank of the TopN index");
   m.def("topn_index", &topn_index, "build pass of the device TopN slot index (count or fill)");

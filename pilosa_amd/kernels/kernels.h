@@ -43,8 +43,14 @@ struct ViewDev {
   // shadow + ((shadow_slot[d] * S + s) * 16 + j) * 1024; nullptr / -1 = none
   const uint64_t* shadow;
   const int32_t* shadow_slot;  // [D]
+  // bitmap twins of the view's dense ARRAY rows (pair kernels, TWN): the
+  // shadow's address layout with twin_slot in place of shadow_slot; used for a
+  // container only while it is an array of more than twin_cutoff values
+  const uint64_t* twin;
+  const int32_t* twin_slot;    // [D]
+  int64_t twin_cutoff;
 };
-static_assert(sizeof(ViewDev) == 64, "ViewDev layout");
+static_assert(sizeof(ViewDev) == 88, "ViewDev layout");
 
 struct BsiArgs {
   int32_t view;

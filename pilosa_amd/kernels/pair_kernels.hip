@@ -49,6 +49,19 @@
 // branch-free clamped loads, the stage's first load before the LDS clear)
 // measured 23.5 vs 16.7 ms (profiles/r03_pf/): like v9, issuing the array
 // loads earlier made the kernel slower, not faster.
+// Bitmap twins (TWN, variant 63, shipped at 64 queries per wave): the dense
+// array containers (n > T) of up to 64 mostly-array rows also live in HBM as
+// bitmaps and either side of a pair reads its twin, so a dense B is 8
+// ds_read_b128 ANDs instead of n ds_read_b32 gathers and a dense A stages by
+// one copy.  kbench, min of 10 (profiles/pairs_twin/): plain v6 16.29-16.30 ms
+// (five alternated repeats); T = 3072 / 2730 / 2048: 15.86 / 15.59 / 15.05 ms
+// with 12 / 19 / 35 twin rows (1.4 / 2.2 / 4.1 GiB, built in 1.4 ms); at 2048
+// twinned A only 16.16, B only 15.40.  LDS instructions -27 %, VALU -17 %,
+// fetched bytes +12 %.  Un-staging (UNS, variants 64 / 65: zero only the
+// dwords a <= 512-value array set instead of the 8 KiB clear) measured
+// SLOWER, 16.73 vs 16.30 ms alone and 15.42 vs 15.05 ms on top of the twins
+// (8 predicated, conflicting ds_write_b32 and 8 more VGPRs against 8 b128
+// stores): built into the kbench module only.
 //
 // Reference hot loops replaced: roaring/roaring.go:3078-3215 intersectionCount*
 // and executor.go:1230-1290 (executeCount over executeIntersect).
@@ -618,9 +631,9 @@ __device__ __forceinline__ int count_global_vs_head(uint64_t* lb, const uint64_t
   return runs_in_lds(lb, pB);
 }
 
-#ifdef PK_KBENCH
 // shadow[r][s][j]: row rows[r]'s key-j container of shard s as a bitmap (zeros
 // where absent).  One wave per (r, s, j): built in LDS by stage(), copied out.
+// Builds the bitmap twins (TWN, below) too: same layout, other rows.
 __global__ __launch_bounds__(64) void shadow_build_kernel(ViewDev v, int S, const int32_t* __restrict__ rows, int R,
                                                           uint64_t* __restrict__ shadow) {
   __shared__ uint64_t lb[1024];
@@ -651,7 +664,71 @@ __global__ __launch_bounds__(64) void shadow_build_kernel(ViewDev v, int S, cons
   for (int i = 0; i < 8; i++) dst[i * 64 + lane] = l2[lds_swzc(uint32_t(i * 64 + lane))];
 }
 
-#endif  // PK_KBENCH
+// ---- un-staging (UNS): an array A of <= 512 values is staged from ONE
+// 16-byte chunk per lane.  The wave keeps that chunk (4 VGPRs); while lb holds
+// exactly those values (kn > 0), the next array is staged after storing zero
+// to the dwords the kept values set -- at most 8 ds_write_b32 per lane --
+// instead of the 8 ds_write_b128 of lds_clear().  Anything else written to lb
+// (a bitmap copy, a bigger array, runs, a staged B) leaves kn = 0 and the next
+// array staging clears as before.
+__device__ __forceinline__ void stage_uns(uint64_t* lb, const uint16_t* p, int64_t m, uint4& kc, int& kn) {
+  if (meta_type(m) != CT_ARRAY) {
+    stage<false, false>(lb, p, m);
+    kn = 0;
+    return;
+  }
+  const int lane = lane_id();
+  uint32_t* l32 = reinterpret_cast<uint32_t*>(lb);
+  if (kn > 0) {
+    const uint32_t w[4] = {kc.x, kc.y, kc.z, kc.w};
+    const int rem = kn - lane * 8;   // <= 0 on lanes that held no chunk
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t v = (w[k >> 1] >> ((k & 1) * 16)) & 0xffff;
+      if (k < rem) l32[lds_swz(v >> 5)] = 0u;
+    }
+  } else {
+    lds_clear(lb);
+  }
+  lds_wait();
+  const int n = meta_n(m);
+  const auto p4 = gp(reinterpret_cast<const uint4*>(p));
+  const int n8 = (n + 7) >> 3;
+  const bool keep = n <= 512;   // one chunk per lane: the loop body runs at most once
+  for (int e8 = lane; e8 < n8; e8 += 64) {
+    const uint4 v4 = p4[e8];
+    if (keep) kc = v4;
+    const uint32_t w[4] = {v4.x, v4.y, v4.z, v4.w};
+    const int rem = n - e8 * 8;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint32_t v = (w[k >> 1] >> ((k & 1) * 16)) & 0xffff;
+      atomicOr(l32 + lds_swz(v >> 5), k < rem ? (1u << (v & 31)) : 0u);
+    }
+  }
+  kn = keep ? n : 0;
+  lds_wait();
+}
+
+// ---- bitmap twins (TWN): the dense ARRAY containers (n > the view's
+// twin_cutoff) of the rows DeviceView.ensure_twin picked also exist as
+// 1024-word bitmaps in HBM.  The prologue swaps such an operand's payload
+// pointer for its twin and rewrites the lane's meta type to CT_BITMAP, on
+// side A (TWN & 1), side B (TWN & 2) or both; everything after the prologue
+// then takes its bitmap path: a twinned B is 8 conflict-free ds_read_b128
+// ANDs instead of n ds_read_b32 gathers, a twinned A stages by one copy with
+// no clear and no ds_or scatter.  Costs 8 KiB of reads instead of 2 n bytes.
+__device__ __forceinline__ int64_t meta_as_bitmap(int64_t m) {
+  return (m & ~(int64_t(3) << 4)) | (int64_t(CT_BITMAP) << 4);
+}
+
+__device__ __forceinline__ void twin_swap(const ViewDev& v, int64_t d, int S, int64_t u, int64_t& m, uint64_t& pl) {
+  if (v.twin_slot == nullptr || meta_type(m) != CT_ARRAY || meta_n(m) <= v.twin_cutoff) return;
+  const int sl = gp(v.twin_slot)[d];
+  if (sl < 0) return;
+  pl = reinterpret_cast<uint64_t>(v.twin + ((int64_t(sl) * S + (u >> 4)) * 16 + (u & 15)) * 1024);
+  m = meta_as_bitmap(m);
+}
 
 // Array A of <= 512 values staged from its chunk already in registers (one
 // 16-byte chunk per lane, loaded while the previous pair was counted).
@@ -704,11 +781,12 @@ __device__ __forceinline__ void stage_array_head(uint64_t* lb, int64_t m, const 
 // global gathers, no 8 KiB LDS copy), and of two arrays the smaller one is
 // staged and the larger probes it.
 template <int CQ, bool APF = false, int DBG = 0, int SB = 0, int PD = 1, bool ONE = false, bool BST = false,
-          bool SHD = false, bool ROT = false>
+          bool SHD = false, bool ROT = false, int TWN = 0, bool UNS = false>
 __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* __restrict__ progs, int Q,
                                                              const ViewDev* __restrict__ views, int S,
                                                              const uint2* __restrict__ pairs,
                                                              int32_t* __restrict__ partial) {
+  static_assert(!UNS || (!APF && DBG == 0 && !BST && !SHD && !ROT), "UNS builds on the plain v6 staging");
   __shared__ uint64_t lb[1024];
   const int lane = lane_id();
   const int64_t gw = int64_t(xcd_remap_blocks(blockIdx.x, gridDim.x));
@@ -737,6 +815,8 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
         const int sl = gp(views[vai].shadow_slot)[progs[q0 + lane].leaf_row[0]];
         if (sl >= 0) sha = reinterpret_cast<uint64_t>(views[vai].shadow + ((int64_t(sl) * S + (u >> 4)) * 16 + (u & 15)) * 1024);
       }
+      if (TWN & 1) twin_swap(views[vai], progs[q0 + lane].leaf_row[0], S, u, ma, pal);
+      if (TWN & 2) twin_swap(views[vbi], progs[q0 + lane].leaf_row[1], S, u, mb, pbl);
     }
   }
   uint64_t todo = __ballot(ea != NONE);
@@ -745,6 +825,8 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
   if (todo) {
     uint32_t cached = NONE;
     int cached_v = -1;
+    uint4 kc = make_uint4(0, 0, 0, 0);   // UNS: the staged small array's chunk
+    int kn = 0;                          // its size; 0 = lb holds anything else
     int i = __builtin_ctzll(todo);
     todo &= todo - 1;
     // pf[k]: head of the k-th pair from the current one (k = 0: pair i)
@@ -865,6 +947,7 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
         } else if (!next_same && tA == CT_ARRAY && tB == CT_BITMAP) {
           lds_wait();
           stage<BST, ROT>(lb, pB, mB);
+          if (UNS) kn = 0;
           cached = NONE;
           cached_v = -1;
           c = count_vs_lds<ROT>(lb, pA, mA);
@@ -884,6 +967,7 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
           // the smaller array is staged, the larger one probes it
           lds_wait();
           stage<BST, ROT>(lb, pB, mB);
+          if (UNS) kn = 0;
           cached = NONE;
           cached_v = -1;
           c = count_vs_lds<ROT>(lb, pA, mA);
@@ -891,6 +975,8 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
           lds_wait();  // previous readers of lb are done before it is rewritten
           if (APF && aok && small_array(mA))
             stage_array_head<ROT>(lb, mA, ahead);
+          else if (UNS)
+            stage_uns(lb, pA, mA, kc, kn);
           else
             stage<BST, ROT>(lb, pA, mA);
           cached = a;
@@ -1172,14 +1258,21 @@ void launch_v6_dbg(int dbg, int64_t wv, const QueryProg* progs, int Q, const Vie
   }
 }
 
+#endif  // PK_KBENCH
+
+template <int TWN, bool UNS>
+void launch_v6_twn(int64_t wv, const QueryProg* progs, int Q, const ViewDev* views, int S, uint2* pairs,
+                   int32_t* partial, hipStream_t st) {
+  hipLaunchKernelGGL((and2_pairs_v6_kernel<64, false, 0, 0, 1, false, false, false, false, TWN, UNS>),
+                     dim3(unsigned(wv)), dim3(64), 0, st, progs, Q, views, S, pairs, partial);
+}
+
 void launch_shadow_build(const ViewDev& v, int S, const int32_t* rows, int R, uint64_t* shadow, hipStream_t st) {
   const int64_t w = int64_t(R) * S * 16;
   if (w <= 0) return;
   const dim3 grid(unsigned(w < 65535 ? w : 65535), unsigned((w + 65534) / 65535));
   hipLaunchKernelGGL(shadow_build_kernel, grid, dim3(64), 0, st, v, S, rows, R, shadow);
 }
-
-#endif  // PK_KBENCH
 
 void launch_keymask_build(const ViewDev& v, int S, uint16_t* out, hipStream_t st) {
   const int64_t n = int64_t(S) * v.D;
@@ -1198,6 +1291,30 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
   hipLaunchKernelGGL(pair_build_kernel, dim3(unsigned((items + 255) / 256)), dim3(256), 0, st, progs, Q, views, S,
                      pairs);
   const int64_t units = int64_t(S) * 16;
+  // bitmap twins / un-staging: v6 at 64 queries per wave only -- 61 twinned A,
+  // 62 twinned B, 63 both (shipped), 64 un-staging, 65 both twins +
+  // un-staging.  Any other chunk size runs the plain kernels below.  The
+  // shipped build holds 63 alone (binding.cpp PAIR_VARIANTS, which the
+  // engine consults before it asks for another one).
+  if (variant >= 61 && variant <= 65) {
+    if (cq > 0 ? cq != 64 : Q <= 2048) {
+      variant = 6;
+    } else {
+      const int64_t wv = units * ((Q + 63) / 64);
+      switch (variant) {
+#ifdef PK_KBENCH
+        case 61: launch_v6_twn<1, false>(wv, progs, Q, views, S, pairs, partial, st); break;
+        case 62: launch_v6_twn<2, false>(wv, progs, Q, views, S, pairs, partial, st); break;
+        case 64: launch_v6_twn<0, true>(wv, progs, Q, views, S, pairs, partial, st); break;
+        case 65: launch_v6_twn<3, true>(wv, progs, Q, views, S, pairs, partial, st); break;
+#else
+        case 64: launch_v6_twn<0, false>(wv, progs, Q, views, S, pairs, partial, st); break;
+#endif
+        default: launch_v6_twn<3, false>(wv, progs, Q, views, S, pairs, partial, st); break;
+      }
+      return;
+    }
+  }
   // serving-size batches (<= 128 queries: almost every pair is one-off):
   // batched array staging (variant 39: an array's chunk loads all in flight
   // before the LDS scatter) at 4 queries per wave up to 32 queries, 32 up to
@@ -1214,7 +1331,8 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
 #endif
   if (variant == 41 && cq <= 0 && Q <= 128) variant = 42;   // the same with dense shadows
   if (cq <= 0) cq = Q <= 128 ? 8 : (Q <= 2048 ? 32 : 64);
-// The shipped build instantiates v6 and its serving variant 39 only; every
+// The shipped build instantiates v6, its serving variant 39 and (above) the
+// bitmap-twin variant 63 only; every
 // measured-and-rejected variant and cost-isolation skeleton (v10-v13,
 // 16-24, 31-38, 40-42, 50/51) is built into the kbench module alone
 // (pilosa_amd/native/build.py --kbench, scripts/kbench.py).

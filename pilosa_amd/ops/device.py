@@ -48,11 +48,13 @@ _OPS = {"and": OP_AND, "or": OP_OR, "xor": OP_XOR, "andnot": OP_ANDNOT}
 QPROG_DTYPE = np.dtype([("nleaf", "<i4"), ("nprog", "<i4"), ("leaf_view", "<i4", (MAXLEAF,)),
                         ("leaf_row", "<i8", (MAXLEAF,)), ("prog", "u1", (MAXPROG,)), ("pad", "<i8", (3,))])
 VIEWDEV_DTYPE = np.dtype([("rowptr", "<u8"), ("shard_base", "<u8"), ("meta", "<u8"), ("payload", "<u8"),
-                          ("D", "<i8"), ("keymask", "<u8"), ("shadow", "<u8"), ("shadow_slot", "<u8")])
-assert QPROG_DTYPE.itemsize == 256 and VIEWDEV_DTYPE.itemsize == 64
+                          ("D", "<i8"), ("keymask", "<u8"), ("shadow", "<u8"), ("shadow_slot", "<u8"),
+                          ("twin", "<u8"), ("twin_slot", "<u8"), ("twin_cutoff", "<i8")])
+assert QPROG_DTYPE.itemsize == 256 and VIEWDEV_DTYPE.itemsize == 88
 
 _ext = None
 _ext_lock = threading.Lock()
+_twin_lock = threading.Lock()
 _D2H_POLL = float(os.environ.get("PILOSA_D2H_POLL", "0"))
 
 
@@ -856,8 +858,9 @@ class DeviceView:
     def nbytes(self) -> int:
         n = sum(t.numel() * t.element_size() for t in (self.t_rowptr, self.t_shard_base, self.t_meta,
                                                        self.t_payload))
-        sh = getattr(self, "_shadow", None)
-        return n + (sh[1].numel() * 8 + sh[2].numel() * 4 if sh is not None else 0)
+        for sh in (getattr(self, "_shadow", None), getattr(self, "_twin", None)):
+            n += sh[1].numel() * 8 + sh[2].numel() * 4 if sh is not None else 0
+        return n
 
     def dense(self, row: int) -> int:
         """row id -> dense index (-1 if the row has no containers on this GPU)."""
@@ -890,6 +893,11 @@ class DeviceView:
         if sh is not None and sh[0] == self.generation:
             rec["shadow"] = sh[1].data_ptr()
             rec["shadow_slot"] = sh[2].data_ptr()
+        tw = getattr(self, "_twin", None)
+        if tw is not None and tw[0] == self.generation:
+            rec["twin"] = tw[1].data_ptr()
+            rec["twin_slot"] = tw[2].data_ptr()
+            rec["twin_cutoff"] = tw[5]
         return rec
 
     def shadow_fresh(self) -> bool:
@@ -969,6 +977,83 @@ class DeviceView:
         self._shadow = (self.generation, buf, slot, now, rows)
         return True
 
+    # bitmap twins of dense ARRAY rows (pair_kernels.hip TWN): up to TWIN_ROWS
+    # rows, within a quarter of free HBM; a container is read through its twin
+    # only while it is an array of more than TWIN_CUTOFF values
+    TWIN_ROWS = int(os.environ.get("PILOSA_TWIN_ROWS", "64"))
+    TWIN_CUTOFF = int(os.environ.get("PILOSA_TWIN_CUTOFF", "2048"))
+    TWIN_MIN_INTERVAL_S = 30.0
+
+    def twin_fresh(self) -> bool:
+        tw = getattr(self, "_twin", None)
+        return tw is not None and tw[0] == self.generation
+
+    def _twin_sample(self):
+        """(rowptr int64[D+1], meta int64[n]) of the sampled shards (the
+        sample of :meth:`_hot_dense_rows`)."""
+        D1 = self.D + 1
+        picks = sorted(set(np.linspace(0, self.S - 1, min(self.S, self.SHADOW_SAMPLE_SHARDS)).astype(int).tolist()))
+        out = []
+        for si in picks:
+            rp = self.t_rowptr[si * D1:(si + 1) * D1].cpu().numpy().astype(np.int64)
+            b = int(self._sb_host[si])
+            out.append((rp, self.t_meta[b:b + int(rp[-1])].cpu().numpy()))
+        return out
+
+    def ensure_twin(self) -> bool:
+        """Build (or refresh, at most every TWIN_MIN_INTERVAL_S after writes)
+        the bitmap twins of this view's dense array rows
+        (:func:`select_twin_rows`): every (shard, key) container of such a row
+        as a 1024-word bitmap in HBM, laid out like the shadows.  The pair
+        kernel reads a twin instead of an array container of more than
+        TWIN_CUTOFF values, on either side of a pair.  The twin is tied to
+        the view generation and a stale one is not passed, so answers never
+        depend on it.  Returns whether it is fresh."""
+        import time
+
+        import torch
+
+        if self.TWIN_ROWS <= 0 or self.device.type != "cuda" or not self.S or not self.D:
+            return False
+        if self.twin_fresh():
+            return True
+        with _twin_lock:   # request threads: one build, the others find it fresh
+            return self._build_twin(time, torch)
+
+    def _build_twin(self, time, torch) -> bool:
+        tw = getattr(self, "_twin", None)
+        if tw is not None and tw[0] == self.generation:
+            return True
+        now = time.monotonic()
+        if tw is not None and now - tw[3] < self.TWIN_MIN_INTERVAL_S:
+            return False
+        if tw is None and getattr(self, "_twin_declined", None) == self.generation:
+            return False
+        per_row = self.S * 16 * 8192
+        held = tw[1].numel() * 8 if tw is not None else 0
+        free, _ = torch.cuda.mem_get_info(self.device)
+        R = min(self.TWIN_ROWS, 64, self.D, int((free + held) // 4 // per_row))
+        cutoff = int(self.TWIN_CUTOFF)
+        rows = select_twin_rows(self._twin_sample(), self.D, cutoff, R) if R > 0 else np.zeros(0, np.int32)
+        if len(rows) == 0:
+            self._twin = None
+            self._twin_declined = self.generation
+            return False
+        R = len(rows)
+        buf = tw[1] if tw is not None and tw[1].numel() == R * self.S * 16 * 1024 else None
+        if buf is None:
+            self._twin = tw = None
+            buf = torch.empty(R * self.S * 16 * 1024, dtype=torch.int64, device=self.device)
+        slot = torch.full((self.D,), -1, dtype=torch.int32)
+        slot[torch.from_numpy(rows.astype(np.int64))] = torch.arange(R, dtype=torch.int32)
+        slot = slot.to(self.device)
+        self.ensure_keymask()
+        kernels().twin_build(self.viewdev_tensor(), self.S, torch.from_numpy(rows).to(self.device), buf)
+        # readers on any stream see a complete twin
+        torch.cuda.current_stream(self.device).synchronize()
+        self._twin = (self.generation, buf, slot, now, rows, cutoff)
+        return True
+
     def viewdev_tensor(self):
         """The ViewDev record as the uint8 host tensor the kernel bindings take."""
         import torch
@@ -1002,8 +1087,8 @@ class DeviceView:
             # whose row directory is large next to their containers, or when
             # it would not leave the device comfortably free
             need = 2 * n
-            sh = getattr(self, "_shadow", None)
-            arena = self.nbytes() - (sh[1].numel() * 8 + sh[2].numel() * 4 if sh is not None else 0)
+            arena = sum(t.numel() * t.element_size() for t in (self.t_rowptr, self.t_shard_base, self.t_meta,
+                                                                   self.t_payload))
             if need > max(256 << 20, arena // 4):
                 return False
             free, _ = torch.cuda.mem_get_info(self.device)
@@ -1020,6 +1105,33 @@ class DeviceView:
         kernels().keymask_build(torch.from_numpy(np.frombuffer(rec.tobytes(), dtype=np.uint8).copy()), self.S, out)
         self._keymask = (self.generation, out, now)
         return True
+
+
+def select_twin_rows(sample, D: int, cutoff: int, max_rows: int) -> np.ndarray:
+    """Dense rows worth a bitmap twin, from ``sample`` = [(rowptr int64[D+1],
+    meta int64[n])] of a few shards: rows whose sampled containers are mostly
+    arrays (more than half) and whose array containers hold more than
+    ``cutoff`` values on average.  At most ``max_rows`` rows, those with the
+    most array values first; returned sorted, int32."""
+    cnt = np.zeros(D, np.int64)
+    arr = np.zeros(D, np.int64)
+    bits = np.zeros(D, np.int64)
+    for rp, m in sample:
+        rp = np.asarray(rp, np.int64)
+        m = np.asarray(m, np.int64)[:int(rp[-1])]
+        if len(m) == 0:
+            continue
+        row = np.repeat(np.arange(D, dtype=np.int64), np.diff(rp))
+        is_arr = ((m >> 4) & 3) == 1
+        card = (m >> 6) & 0x1FFFF
+        cnt += np.bincount(row, minlength=D)
+        arr += np.bincount(row, weights=is_arr, minlength=D).astype(np.int64)
+        bits += np.bincount(row, weights=np.where(is_arr, card, 0), minlength=D).astype(np.int64)
+    ok = (arr * 2 > cnt) & (bits > np.int64(cutoff) * arr)
+    idx = np.nonzero(ok)[0]
+    if len(idx) > max_rows:
+        idx = idx[np.argsort(-bits[idx], kind="stable")[:max(max_rows, 0)]]
+    return np.sort(idx).astype(np.int32)
 
 
 # ---------------------------------------------------------------- engine
@@ -1062,10 +1174,31 @@ class GpuEngine:
         # dense shadows of hot rows (variants 41 / 42): measured slower, built
         # into the kbench module only (profiles/r05_shadow/)
         self.use_shadow = os.environ.get("PILOSA_SHADOW", "0") != "0" and hasattr(kernels(), "shadow_build")
+        # the 64-queries-per-wave pair kernel reads dense array rows through
+        # their bitmap twins (DeviceView.ensure_twin, pair_kernels.hip TWN:
+        # 15.05 vs 16.30 ms per 4096-query headline batch).  Un-staging of
+        # small arrays (UNS) measured slower (16.73 ms) and is built into the
+        # kbench module only (profiles/pairs_twin/)
+        built = set(getattr(kernels(), "PAIR_VARIANTS", ()))
+        self.use_twin = os.environ.get("PILOSA_TWIN", "1") != "0" and 63 in built
+        self.use_unstage = os.environ.get("PILOSA_UNSTAGE", "0") != "0" and {64, 65} <= built
         # Count(Union(leaves)) route: union_count_kernel (bitmap_kernels.hip)
         self.use_union = os.environ.get("PILOSA_UNION_KERNEL", "1") != "0"
         # 2 = union_count2_kernel (flat chunk walk, parallel meta fetch), 1 = union_count_kernel
         self.union_variant = int(os.environ.get("PILOSA_UNION_VARIANT", "2"))
+
+    def _and2_aux(self, views: List["DeviceView"], n: int) -> int:
+        """Side structures of a batch with ``n`` Count(Intersect) queries: 1 =
+        a view carries dense shadows, 2 = a view carries fresh bitmap twins, 0
+        = neither.  Twins are ensured only for batches that run the
+        64-queries-per-wave pair kernel."""
+        if self.use_shadow and any([v.ensure_shadow() for v in views]):
+            return 1
+        wave64 = self.and2_cq == 64 or (self.and2_cq <= 0 and n > 2048)
+        if self.use_twin and wave64 and self.and2_variant in (6, 61, 62, 63, 65) and \
+                any([v.ensure_twin() for v in views]):
+            return 2
+        return 0
 
     def _views_tensor(self, views: List["DeviceView"]):
         arr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
@@ -1203,7 +1336,7 @@ class GpuEngine:
             lr = progs["leaf_row"]
             for v in views:
                 v.ensure_keymask()
-        shd = bool(is_and2.any()) and self.use_shadow and any([v.ensure_shadow() for v in views])
+        shd = self._and2_aux(views, int(is_and2.sum())) if is_and2.any() else 0
         varr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
         for i, v in enumerate(views):
             varr[i] = v.viewdev()
@@ -1231,11 +1364,12 @@ class GpuEngine:
         torch = self.torch
         if not S or not Q:
             return (Q, S, None, [])
-        shd = False
-        if any(int(kind) == KIND_AND2 for kind, _, _, _ in segs):
+        shd = 0
+        n_and2 = sum(int(n) for kind, n, _, _ in segs if int(kind) == KIND_AND2)
+        if n_and2:
             for v in views:
                 v.ensure_keymask()
-            shd = self.use_shadow and any([v.ensure_shadow() for v in views])
+            shd = self._and2_aux(views, n_and2)
         varr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
         for i, v in enumerate(views):
             varr[i] = v.viewdev()
@@ -1267,14 +1401,21 @@ class GpuEngine:
                 col[swap, 0], col[swap, 1] = col[swap, 1].copy(), col[swap, 0].copy()
         return progs
 
-    def _and2_partial(self, tp, tv, S: int, n: int, shd: bool = False):
+    def _and2_partial(self, tp, tv, S: int, n: int, shd: int = 0):
         """Per-(shard, key, query) Count(Intersect) partials -> int32[S, 16, n].
-        ``shd``: a view of the batch carries dense shadows (variant 41; the
-        launcher takes 42 for serving-size batches)."""
+        ``shd`` (:meth:`_and2_aux`) 1: a view of the batch carries dense
+        shadows (variant 41; the launcher takes 42 for serving-size batches);
+        2: a view carries fresh bitmap twins (variant 63, with un-staging 65;
+        the launcher runs them at 64 queries per wave only)."""
         torch = self.torch
         pairs = torch.empty(S * 16 * n * 2, dtype=torch.int32, device=self.device)
         partial = torch.empty(S * 16 * n, dtype=torch.int32, device=self.device)
-        variant = 41 if shd and self.and2_variant == 6 else self.and2_variant
+        variant = self.and2_variant
+        if variant == 6 and shd == 1:
+            variant = 41
+        elif variant == 6:
+            variant = {(True, True): 65, (True, False): 63, (False, True): 64}.get(
+                (shd == 2 and self.use_twin, self.use_unstage), 6)
         self.ext.and2_count(tp, tv, S, pairs, partial, self.and2_cq, variant)
         return partial.view(S, 16, n)
 

@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Kernel-level A/B harness on the headline dataset: times the device half
 (launch_count) of a Count(Intersect) batch for several engine settings with
-HIP events.  Usage: python scripts/kbench.py [--batch 1024] [--reps 5] [--shards N]"""
+HIP events.  Usage: python scripts/kbench.py [--batch 1024] [--reps 5] [--shards N]
+
+Pair-kernel variant ids of the bitmap twins / un-staging (64 queries per
+wave): 61 twinned A only, 62 twinned B only, 63 both, 64 un-staging only, 65
+both twins + un-staging; --twin-cutoff lists the cutoffs T each twin variant
+is timed at (the twin is rebuilt per T).  6 = the plain v6 kernel; a variant
+may be listed several times to alternate it with others."""
 import argparse
 import json
 import math
@@ -28,6 +34,8 @@ def main():
     ap.add_argument("--cq", default="0,32,64", help="pair-kernel chunk sizes (queries per wave)")
     ap.add_argument("--no-tile", action="store_true", help="skip the generic tile kernel")
     ap.add_argument("--variants", default="", help="extra kernel variants at --cq's first size, e.g. 4,5 (38@8: at 8 queries per wave)")
+    ap.add_argument("--twin-cutoff", default="", help="twin cutoffs T for variants 61/62/63/65, e.g. 3072,2730,2048 "
+                    "(default: DeviceView.TWIN_CUTOFF)")
     args = ap.parse_args()
     import torch
 
@@ -54,12 +62,28 @@ def main():
             continue
         vv, _, cq = v.partition("@")   # "38@8": variant 38 at 8 queries per wave
         cq = int(cq) if cq else cq0
-        configs.append((f"and2var{vv}_cq{cq}", {"and2_cq": cq, "and2_variant": int(vv)}))
+        cuts = [int(t) for t in args.twin_cutoff.split(",") if t] if int(vv) in (61, 62, 63, 65) else []
+        for t in cuts or [None]:
+            name = f"and2var{vv}_cq{cq}" + (f"_t{t}" if t is not None else "")
+            while name in [c[0] for c in configs]:
+                name += "'"      # a repeat of the same setting (alternating runs)
+            configs.append((name, {"and2_cq": cq, "and2_variant": int(vv), "twin_cutoff": t}))
     for name, cfg in configs:
         eng = GpuEngine(dev)
+        cut = cfg.pop("twin_cutoff", None)
         for k, v in cfg.items():
             setattr(eng, k, v)
+        eng.use_unstage = eng.use_twin = False      # variants are explicit here: 6 is the plain kernel
+        eng.use_twin = cfg.get("and2_variant") in (61, 62, 63, 65)
+        if cut is not None and (view.TWIN_CUTOFF != cut or not view.twin_fresh()):
+            view._twin = None        # rebuilt at this cutoff by prepare_progs
+            view.TWIN_CUTOFF = cut
+        t0 = time.perf_counter()
         h = eng.prepare_progs(progs, views, S)
+        if cut is not None and view.twin_fresh():
+            tw = view._twin
+            print(f"twin T={cut}: {len(tw[4])} rows, {tw[1].numel() * 8 / 2**30:.2f} GiB, "
+                  f"prepare+build {time.perf_counter() - t0:.3f} s", flush=True)
         out = eng.launch_count(h)
         torch.cuda.synchronize()
         got = out.cpu().numpy()

@@ -3,7 +3,11 @@
 arena / batch as scripts/kbench.py): per (unit, 64-query chunk) the v6 walk
 -- pairs, stagings of A (a new leaf-0 container), A and B types and sizes,
 run lengths -- so kernel restructures can be priced before they are built.
-Usage: python scripts/pair_stats.py [--sample 2] [--batch 4096]"""
+Also: LDS probes (one per array B value) per B size class, array stagings per
+A size class, and the pairs / probes / stagings whose A or B container a
+bitmap twin at cutoff T would replace (rows picked by select_twin_rows over
+the sampled shards, containers by n > T) with the bytes that adds.
+Usage: python scripts/pair_stats.py [--sample 2] [--batch 4096] [--twin-cutoff 3072,2730,2048]"""
 import argparse
 import collections
 import json
@@ -21,8 +25,10 @@ def main():
     ap.add_argument("--sample", type=int, default=2)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--cq", type=int, default=64)
+    ap.add_argument("--twin-cutoff", default="3072,2730,2048")
     args = ap.parse_args()
     from pilosa_amd import _roaring
+    from pilosa_amd.ops.device import select_twin_rows
     rows, rowptr, sb, meta, payload = _roaring.gen_zipf_arena(0, args.sample, TOTAL_COLS, NROWS, 8.0, 1.6, 50.0, 1, 8)
     rows = np.asarray(rows, np.uint64)
     D = len(rows)
@@ -48,6 +54,22 @@ def main():
     na_stage_hist = collections.Counter()
     runlen = collections.Counter()
     pairs_per_wave = []
+    cuts = [int(t) for t in args.twin_cutoff.split(",") if t]
+    sample = [(rp[s], meta[sb[s]:sb[s] + rp[s, -1]]) for s in range(args.sample)]
+    twin_rows = {t: set(select_twin_rows(sample, D, t, 64).tolist()) for t in cuts}
+    probes = collections.Counter()        # array B values probed, per B size class
+    stage_cls = collections.Counter()     # array A stagings per size class
+    tw = {t: collections.Counter() for t in cuts}
+    ref_bytes = 0                         # bytes the kernel references (A per staging, B per pair)
+
+    def size_class(x):
+        for b in (512, 1024, 2048, 2730):
+            if x <= b:
+                return f"<={b}"
+        return ">2730"
+
+    def cbytes(t_, n_):
+        return 8192 if t_ == 2 else 2 * int(n_)
 
     def bucket(x):
         for b in (16, 64, 256, 512, 1024, 2048, 4096):
@@ -82,6 +104,21 @@ def main():
                     st[f"pair {('-', 'arr', 'bmp', 'run')[ta]}&{('-', 'arr', 'bmp', 'run')[tb]}"] += 1
                     if tb == 1:
                         nb_hist[bucket(int(n[ib]))] += 1
+                        probes[size_class(int(n[ib]))] += int(n[ib])
+                    ref_bytes += cbytes(tb, n[ib])
+                    da, db = dense.get(int(A[q])), dense.get(int(B[q]))
+                    for t in cuts:
+                        a_tw = ta == 1 and n[ia] > t and da in twin_rows[t]
+                        b_tw = tb == 1 and n[ib] > t and db in twin_rows[t]
+                        tw[t]["pairs_A_twinned"] += a_tw
+                        tw[t]["pairs_B_twinned"] += b_tw
+                        tw[t]["pairs_A_or_B_twinned"] += a_tw or b_tw
+                        if b_tw:
+                            tw[t]["probes_removed"] += int(n[ib])
+                            tw[t]["extra_bytes"] += 8192 - 2 * int(n[ib])
+                        if a_tw and ia != prev:
+                            tw[t]["array_stagings_removed"] += 1
+                            tw[t]["extra_bytes"] += 8192 - 2 * int(n[ia])
                     if ia != prev:
                         if prev is not None:
                             runlen[min(run, 64)] += 1
@@ -90,6 +127,8 @@ def main():
                         st[f"stage {('-', 'arr', 'bmp', 'run')[ta]}"] += 1
                         if ta == 1:
                             na_stage_hist[bucket(int(n[ia]))] += 1
+                            stage_cls[size_class(int(n[ia]))] += 1
+                        ref_bytes += cbytes(ta, n[ia])
                         prev = ia
                     run += 1
                 if prev is not None:
@@ -99,6 +138,12 @@ def main():
     out = {k: round(v * f) for k, v in sorted(st.items())}
     out["B_array_size_hist"] = {k: round(v * f) for k, v in sorted(nb_hist.items())}
     out["A_array_staged_size_hist"] = {k: round(v * f) for k, v in sorted(na_stage_hist.items())}
+    out["B_array_probes_by_size"] = {k: round(v * f) for k, v in probes.items()}
+    out["A_array_stagings_by_size"] = {k: round(v * f) for k, v in stage_cls.items()}
+    out["referenced_bytes"] = round(ref_bytes * f)
+    out["twin"] = {str(t): dict({k: round(int(v) * f) for k, v in sorted(tw[t].items())}, rows=len(twin_rows[t]),
+                                extra_bytes_share=round(tw[t]["extra_bytes"] / max(ref_bytes, 1), 4))
+                   for t in cuts}
     rl = sorted(runlen.items())
     out["run_length_hist"] = {k: round(v * f) for k, v in rl}
     out["one_off_runs"] = round(runlen[1] * f)
