@@ -894,6 +894,69 @@ class Executor:
                 self.logger.printf("gpu detached after %d faults", self.gpu_faults)
             self.gpu = None
 
+    # ================================================================ anti-entropy reads
+    def _block_shards(self, index: str, field: str, view: str, shard: int):
+        """The shard tuple whose device arena answers block reads of this
+        fragment, or None for the host path: no GPU, a mesh node (front end
+        or worker), or a warm fragment no resident arena covers."""
+        g = self.gpu
+        if g is None or self.mesh is not None or getattr(g, "comm", None) is not None or g.device.type != "cuda":
+            return None
+        return g.block_shards(index, field, view, shard)
+
+    def _device_blocks(self, fn):
+        try:
+            return fn()
+        except NotImplementedError:
+            return None
+        except PilosaError:
+            raise
+        except Exception as err:  # noqa: BLE001 - device fault: the host fragments answer
+            self._gpu_fault(err)
+            return None
+
+    def fragment_blocks(self, index: str, field: str, view: str, shard: int, frag) -> list:
+        """``frag.blocks()``, from the device arena where that keeps the
+        fragment cold (ops/gpu_executor.py block_checksums)."""
+        shards = self._block_shards(index, field, view, shard)
+        if shards is not None:
+            res = self._device_blocks(lambda: self.gpu.block_checksums(index, field, view, shards))
+            if res is not None:
+                return res[shard]
+        return frag.blocks()
+
+    def view_blocks(self, index: str, field: str, view: str) -> Dict[int, list]:
+        """{shard: blocks} of every local fragment of the view the device
+        answers for, one ``block_checksums`` call per arena (normally one per
+        view); the shards left out take the host path."""
+        out: Dict[int, list] = {}
+        v = self.holder.view(index, field, view)
+        if v is None or self.gpu is None:
+            return out
+        asked = set()
+        for shard in sorted(list(v.fragments)):
+            if shard in out:
+                continue
+            shards = self._block_shards(index, field, view, shard)
+            if shards is None or shards in asked:
+                continue
+            asked.add(shards)
+            res = self._device_blocks(lambda: self.gpu.block_checksums(index, field, view, shards))
+            if res is None:
+                break
+            out.update((s, b) for s, b in res.items() if s in v.fragments)
+        return out
+
+    def fragment_block_data(self, index: str, field: str, view: str, shard: int, block: int, frag):
+        """``frag.block_data(block)``, dumped from the device arena where
+        that applies."""
+        shards = self._block_shards(index, field, view, shard)
+        if shards is not None:
+            res = self._device_blocks(lambda: self.gpu.block_data(index, field, view, shards, shard, block))
+            if res is not None:
+                return res
+        return frag.block_data(block)
+
     # ================================================================ bitmap calls
     def _bitmap_call(self, index: str, c: Call, shards, opt: ExecOptions) -> Row:
         def reduce_fn(prev, v):

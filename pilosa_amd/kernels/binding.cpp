@@ -986,6 +986,52 @@ void payload_compact(torch::Tensor meta, torch::Tensor new_off16, torch::Tensor 
   check_launch("payload_compact");
 }
 
+// The unit list stays on the host until its ranges are checked against the
+// view (S arena shards, D dense rows): the kernels index rowptr with them.
+torch::Tensor checked_units(const torch::Tensor& units, const pk::ViewDev& v, int64_t S, int64_t M, int64_t e,
+                            const torch::Tensor& rows) {
+  TORCH_CHECK(!units.is_cuda() && units.scalar_type() == torch::kInt32 && units.is_contiguous() &&
+                  units.dim() == 2 && units.size(1) == 3, "units must be a cpu int32[U, 3] tensor");
+  TORCH_CHECK(M >= 1 && S >= 0 && e >= 16 && e <= 32, "block units: M >= 1, 16 <= e <= 32");
+  check_dev(rows, "rows");
+  TORCH_CHECK(rows.scalar_type() == torch::kInt64 && rows.numel() == v.D, "rows int64[D]");
+  const int32_t* p = units.data_ptr<int32_t>();
+  for (int64_t u = 0; u < units.size(0); u++) {
+    const int64_t s0 = p[3 * u], d0 = p[3 * u + 1], d1 = p[3 * u + 2];
+    TORCH_CHECK(s0 >= 0 && s0 + M <= S && d0 >= 0 && d0 <= d1 && d1 <= v.D, "block unit ", u, " out of range");
+  }
+  return units.to(rows.device());
+}
+
+void block_hash(torch::Tensor view, torch::Tensor units, int64_t S, int64_t M, int64_t e, torch::Tensor rows,
+                torch::Tensor out_n, torch::Tensor out_h) {
+  const pk::ViewDev v = viewdev_from(view);
+  const int64_t U = units.size(0);
+  check_dev(out_n, "out_n");
+  check_dev(out_h, "out_h");
+  TORCH_CHECK(out_n.scalar_type() == torch::kInt64 && out_n.numel() == U, "out_n int64[U]");
+  TORCH_CHECK(out_h.scalar_type() == torch::kInt64 && out_h.numel() == U, "out_h int64[U]");
+  if (U == 0) return;
+  const torch::Tensor du = checked_units(units, v, S, M, e, rows);
+  pk::launch_block_hash(v, du.data_ptr<int32_t>(), U, int(M), int(e), rows.data_ptr<int64_t>(),
+                        out_n.data_ptr<int64_t>(), reinterpret_cast<uint64_t*>(out_h.data_ptr<int64_t>()),
+                        cur_stream(rows));
+  check_launch("block_hash");
+}
+
+void block_dump(torch::Tensor view, torch::Tensor unit, int64_t S, int64_t M, int64_t e, torch::Tensor rows,
+                torch::Tensor out) {
+  const pk::ViewDev v = viewdev_from(view);
+  check_dev(out, "out");
+  TORCH_CHECK(out.scalar_type() == torch::kInt64, "out int64[n]");
+  TORCH_CHECK(unit.dim() == 2 && unit.size(0) == 1, "block_dump takes one unit");
+  if (out.numel() == 0) return;
+  const torch::Tensor du = checked_units(unit, v, S, M, e, rows);
+  pk::launch_block_dump(v, du.data_ptr<int32_t>(), int(M), int(e), rows.data_ptr<int64_t>(),
+                        reinterpret_cast<uint64_t*>(out.data_ptr<int64_t>()), out.numel(), cur_stream(rows));
+  check_launch("block_dump");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1049,6 +1095,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("payload_compact", &payload_compact, "copy live containers into a compacted payload buffer");
   m.def("container_emit", &container_emit, "device write path: bitmap -> final run/array/bitmap container (Optimize rule) + metadata");
   m.def("densify", &densify, "dense bit rows of an arena over a shard range");
+  m.def("block_hash", &block_hash, "anti-entropy: position count and XXH64 of (fragment, 100-row block) units");
+  m.def("block_dump", &block_dump, "anti-entropy: one block's positions in ascending order");
   m.def("bsi_sum", &bsi_sum, "bit-sliced integer sum with optional filter program", py::arg("progs"),
         py::arg("views"), py::arg("S"), py::arg("bsi_args"), py::arg("out_sum"), py::arg("out_cnt"),
         py::arg("fmode") = 2);

@@ -210,4 +210,16 @@ void launch_payload_compact(const int64_t* meta, int64_t C, const int64_t* new_o
 void launch_container_emit(const uint64_t* scratch, const int32_t* card, const int32_t* nruns, const int64_t* off16,
                            const int32_t* jkey, int64_t U, uint16_t* payload, int64_t* meta_out, hipStream_t st);
 
+// Anti-entropy read path (sync_kernels.hip).  units[u] = {first arena shard of
+// the fragment, d0, d1}: the dense rows [d0, d1) of one 100-row block over the
+// fragment's M sub-shards; rows[D] = the view's row directory; e = the shard
+// width exponent.  block_hash: out_n[u] = set positions of unit u (0 = no
+// block), out_h[u] = XXH64 over them as big-endian u64 in ascending order
+// (launched in chunks of 2^16 units).  block_dump: one unit's positions
+// row << e | column in that order into out[0 .. cap).
+void launch_block_hash(const ViewDev& v, const int32_t* units, int64_t U, int M, int e, const int64_t* rows,
+                       int64_t* out_n, uint64_t* out_h, hipStream_t st);
+void launch_block_dump(const ViewDev& v, const int32_t* unit, int M, int e, const int64_t* rows, uint64_t* out,
+                       int64_t cap, hipStream_t st);
+
 }  // namespace pk

@@ -1185,14 +1185,16 @@ class Fragment:
             v = self.storage.slice_range(lo, hi)
         return v // np.uint64(SHARD_WIDTH), v % np.uint64(SHARD_WIDTH)
 
-    def merge_block(self, block_id: int, data: List[Tuple[Sequence[int], Sequence[int]]]):
+    def merge_block(self, block_id: int, data: List[Tuple[Sequence[int], Sequence[int]]], local=None):
         """Majority-vote merge of replica block data (fragment.go:1873-1991).
         Returns (sets, clears) diffs per remote replica.  The reference walks
         the replicas' sorted pair iterators in lockstep; here every replica's
         pairs become sorted position arrays (models/iterator.py) and the vote
-        is one counted union over them."""
+        is one counted union over them.  ``local``: this fragment's (rows,
+        cols) of the block when the caller already has them (read from the
+        device arena), so the storage is not read for them."""
         from pilosa_amd.models.iterator import pairs_to_positions
-        lr, lc = self.block_data(block_id)
+        lr, lc = local if local is not None else self.block_data(block_id)
         lo, hi = block_id * HASH_BLOCK_SIZE, (block_id + 1) * HASH_BLOCK_SIZE
         sets_all = [pairs_to_positions(lr, lc)]
         for rows, cols in data:

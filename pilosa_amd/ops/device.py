@@ -1729,6 +1729,70 @@ class GpuEngine:
         idx = torch.nonzero(flags).reshape(-1).cpu().numpy()
         return view.rows[idx]  # the directory is sorted
 
+    # ------------------------------------------------------------ anti-entropy (K22)
+    def _rows_tensor(self, view: "DeviceView"):
+        """The view's row directory on the device (int64 bit patterns of the
+        uint64 ids), re-uploaded when the directory changes."""
+        hit = getattr(view, "_rows_dev", None)
+        if hit is None or hit[0] != view.rows_gen or int(hit[1].numel()) != view.D:
+            t = self.torch.from_numpy(view.rows.view(np.int64).copy()).to(self.device)
+            hit = view._rows_dev = (view.rows_gen, t)
+        return hit[1]
+
+    @staticmethod
+    def block_ranges(view: "DeviceView"):
+        """(block ids, d0, d1): the dense-row range of every 100-row block of
+        the view's sorted row directory."""
+        from pilosa_amd.models.fragment import HASH_BLOCK_SIZE
+        if view.D == 0:
+            z = np.zeros(0, np.int64)
+            return z, z, z
+        bids, d0 = np.unique(view.rows // np.uint64(HASH_BLOCK_SIZE), return_index=True)
+        d0 = d0.astype(np.int64)
+        return bids.astype(np.int64), d0, np.concatenate([d0[1:], [view.D]]).astype(np.int64)
+
+    def block_args(self, view: "DeviceView"):
+        """Launch arguments of the block kernels for the view as it is now (taken
+        under the executor's lock when a refresh may run concurrently)."""
+        from pilosa_amd import shardwidth
+        if self.device.type != "cuda":
+            raise NotImplementedError("block kernels need a GPU")
+        # the launch runs without the executor's lock, like every read launch: the
+        # buffers the record points at are held until the call returns, so a
+        # concurrent refresh that replaces one cannot recycle it under the kernel
+        while True:
+            keep = (view.t_rowptr, view.t_shard_base, view.t_meta, view.t_payload)
+            rec = view.viewdev()
+            if all(int(rec[k]) == t.data_ptr() for k, t in zip(("rowptr", "shard_base", "meta", "payload"), keep)):
+                break
+        vd = self.torch.from_numpy(np.frombuffer(rec.tobytes(), dtype=np.uint8).copy())
+        return vd, view.S, shardwidth.DEVICE_SUBSHARDS, shardwidth.EXPONENT, self._rows_tensor(view), keep
+
+    def block_hash(self, view: "DeviceView", units: np.ndarray, args=None):
+        """Position count (int64[U]) and XXH64 (uint64[U]) of every unit
+        {first arena shard of the fragment, d0, d1} (sync_kernels.hip)."""
+        torch = self.torch
+        units = np.ascontiguousarray(units, dtype=np.int32).reshape(-1, 3)
+        U = len(units)
+        if U == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.uint64)
+        vd, S, M, e, rows, keep = args if args is not None else self.block_args(view)
+        out_n = torch.empty(U, dtype=torch.int64, device=self.device)
+        out_h = torch.empty(U, dtype=torch.int64, device=self.device)
+        self.ext.block_hash(vd, torch.from_numpy(units), S, M, e, rows, out_n, out_h)
+        return out_n.cpu().numpy(), out_h.cpu().numpy().view(np.uint64)
+
+    def block_dump(self, view: "DeviceView", unit, n: int, args=None) -> np.ndarray:
+        """The ``n`` positions row * ShardWidth + column of one unit, ascending."""
+        torch = self.torch
+        if n <= 0:
+            return np.zeros(0, np.uint64)
+        vd, S, M, e, rows, keep = args if args is not None else self.block_args(view)
+        out = torch.empty(int(n), dtype=torch.int64, device=self.device)
+        self.ext.block_dump(vd, torch.from_numpy(np.ascontiguousarray(unit, dtype=np.int32).reshape(1, 3)), S, M, e,
+                            rows, out)
+        return out.cpu().numpy().view(np.uint64)
+
     def bsi_range_count_async(self, bsi_view: "DeviceView", depth: int, op: str, p1: int = 0, p2: int = 0):
         """Count(Row(v <op> x)) without materialising the predicate view:
         device int64[1]."""

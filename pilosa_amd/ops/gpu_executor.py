@@ -197,6 +197,8 @@ class GpuExecutor:
         self._plain_cands: Dict[Tuple, Tuple] = {}
         self.topn_mesh_fused = 0        # mesh cache-only groups answered in one all-reduce
         self._frag_lists: Dict[Tuple, Tuple] = {}   # (index, field, shards) -> (epoch, fragments)
+        # (index, field, view, shard) -> (fragment signature, [(block id, digest)]): block checksums
+        self._block_memo: Dict[Tuple, Tuple] = {}
         self.topn_decline = ""          # why the last topn_batch returned None (diagnostics)
         self._topn_index_why = ""
 
@@ -389,6 +391,109 @@ class GpuExecutor:
             self._topn_indexes.clear()
             self._rank_cache_map.clear()
             self._frag_lists.clear()
+            self._block_memo.clear()
+
+    # ------------------------------------------------------------ anti-entropy (K22)
+    def block_shards(self, index: str, field: str, view: str, shard: int) -> Optional[Tuple[int, ...]]:
+        """The shard tuple to read fragment ``shard``'s blocks with: that of a
+        resident arena of the view covering it (the one the queries use), else
+        -- for a cold fragment -- the view's local shards, so the arena loaded
+        now is the one queries will ask for.  None: the fragment is warm and
+        not resident, the host path answers.  Cold fragments are never put in
+        one arena with warm, non-resident ones: building that arena would read
+        their storage."""
+        with self.mu:
+            for key in reversed(self._arenas):
+                if key[:3] == (index, field, view) and shard in key[3]:
+                    return key[3]
+        v = self.holder.view(index, field, view)
+        frag = v.fragment(shard) if v is not None else None
+        if frag is None or not frag.is_cold():
+            return None
+        return tuple(s for s, f in sorted(dict(v.fragments).items()) if f.is_cold())
+
+    def block_checksums(self, index: str, field: str, view: str, shards: Sequence[int]) -> Dict[int, list]:
+        """{shard: [(block id, 8-byte XXH64 digest), ...]} of the view's
+        fragments, equal to ``Fragment.blocks()`` (fragment.go:1776-1854), read
+        from the view's arena: pending write batches are replayed by
+        ``view_arena`` first, no fragment storage is touched.  Checksums are
+        kept per shard under the fragment signature; only shards whose
+        signature moved are hashed again, all of them in one launch."""
+        shards = shards if type(shards) is tuple else tuple(shards)
+        v = self.holder.view(index, field, view)
+        if v is None:
+            return {int(s): [] for s in shards}
+        # signatures are read BEFORE the arena is brought up to date: the arena
+        # then holds at least that version, so a racing write is re-hashed next time
+        sigs = {}
+        for s in shards:
+            f = v.fragment(s)
+            sigs[s] = (id(f), f.version) if f is not None else None
+        out: Dict[int, list] = {}
+        with self.mu:
+            stale = []
+            for fi, s in enumerate(shards):
+                if sigs[s] is None:
+                    out[int(s)] = []
+                    continue
+                hit = self._block_memo.get((index, field, view, s))
+                if hit is not None and hit[0] == sigs[s]:
+                    out[int(s)] = hit[1]
+                else:
+                    stale.append((fi, s))
+            if not stale:
+                return out
+            # the arena's state is read under the lock (a refresh patches it under
+            # the same lock); the launch itself runs outside it, like every read launch
+            dv = self.view_arena(index, field, view, shards)
+            if dv is None:
+                raise NotImplementedError
+            bids, d0, d1 = GpuEngine.block_ranges(dv)
+            args = self.engine.block_args(dv)
+        M = shardwidth.DEVICE_SUBSHARDS
+        units = np.empty((len(stale), len(bids), 3), np.int32)
+        for k, (fi, _) in enumerate(stale):
+            units[k, :, 0] = fi * M
+            units[k, :, 1] = d0
+            units[k, :, 2] = d1
+        self.launches += 1
+        n, h = self.engine.block_hash(dv, units.reshape(-1, 3), args)
+        digests = h.astype(">u8").tobytes()
+        B = len(bids)
+        for k, (fi, s) in enumerate(stale):
+            blocks = [(int(bids[b]), digests[8 * (k * B + b):8 * (k * B + b) + 8])
+                      for b in np.flatnonzero(n[k * B:(k + 1) * B]).tolist()]
+            with self.mu:
+                self._block_memo[(index, field, view, s)] = (sigs[s], blocks)
+            out[int(s)] = blocks
+        return out
+
+    def block_data(self, index: str, field: str, view: str, shards: Sequence[int], shard: int, block: int):
+        """(rows, cols) uint64 arrays of one block of fragment ``shard``, equal
+        to ``Fragment.block_data`` (fragment.go:1856-1871), dumped from the
+        arena of ``shards`` (which must hold ``shard``)."""
+        from pilosa_amd.models.fragment import HASH_BLOCK_SIZE
+        shards = shards if type(shards) is tuple else tuple(shards)
+        empty = (np.zeros(0, np.uint64), np.zeros(0, np.uint64))
+        if shard not in shards:
+            raise NotImplementedError
+        with self.mu:
+            dv = self.view_arena(index, field, view, shards)
+            if dv is None:
+                return empty
+            d0 = int(np.searchsorted(dv.rows, np.uint64(block * HASH_BLOCK_SIZE)))
+            d1 = int(np.searchsorted(dv.rows, np.uint64((block + 1) * HASH_BLOCK_SIZE)))
+            if d0 == d1:
+                return empty
+            args = self.engine.block_args(dv)
+        unit = np.array([[shards.index(shard) * shardwidth.DEVICE_SUBSHARDS, d0, d1]], np.int32)
+        self.launches += 1
+        n, _ = self.engine.block_hash(dv, unit, args)   # the count pass
+        if int(n[0]) == 0:
+            return empty
+        self.launches += 1
+        pos = self.engine.block_dump(dv, unit, int(n[0]), args)
+        return pos >> np.uint64(shardwidth.EXPONENT), pos & np.uint64(SHARD_WIDTH - 1)
 
     BSI_CACHE = 8
 

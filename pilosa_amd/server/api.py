@@ -367,15 +367,21 @@ class API:
         frag = self.holder.fragment(index, field, view, shard)
         if frag is None:
             raise ErrFragmentNotFound
+        # a cold or device-resident fragment answers from its HBM arena
+        # (Executor.fragment_blocks), the others from their host storage
+        ex = self.executor
+        blocks = ex.fragment_blocks(index, field, view, shard, frag) if ex is not None else frag.blocks()
         # Go encodes []byte as base64 (fragment.go FragmentBlock)
-        return [{"id": b, "checksum": base64.b64encode(c).decode()} for b, c in frag.blocks()]
+        return [{"id": b, "checksum": base64.b64encode(c).decode()} for b, c in blocks]
 
     def fragment_block_data(self, index, field, view, shard, block):
         self.validate("FragmentBlockData")
         frag = self.holder.fragment(index, field, view, shard)
         if frag is None:
             raise ErrFragmentNotFound
-        return frag.block_data(block)
+        ex = self.executor
+        return ex.fragment_block_data(index, field, view, shard, block, frag) if ex is not None \
+            else frag.block_data(block)
 
     def fragment_data(self, index, field, view, shard) -> bytes:
         self.validate("FragmentData")

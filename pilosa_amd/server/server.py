@@ -883,11 +883,20 @@ class Server:
             for f in list(idx.fields.values()):
                 self._sync_attrs(idx.name, f.name, f.row_attr_store)
                 for v in list(f.views.values()):
+                    # the view's local block map comes from its device arena in one
+                    # pass (Executor.view_blocks), taken when the first replicated
+                    # fragment needs it; fragments it leaves out hash on the host
+                    local = None
                     for shard, frag in list(v.fragments.items()):
                         if self._sync_should_abort():
                             return False
-                        self._sync_fragment(idx.name, f.name, v.name, shard, frag)
+                        if local is None and self._replica_owners(idx.name, shard):
+                            local = self.executor.view_blocks(idx.name, f.name, v.name)
+                        self._sync_fragment(idx.name, f.name, v.name, shard, frag, (local or {}).get(shard))
         return True
+
+    def _replica_owners(self, index, shard):
+        return [n for n in self.cluster.shard_nodes(index, shard) if n.id != self.node.id]
 
     def _sync_attrs(self, index, field, store):
         blocks = [{"id": b, "checksum": base64.b64encode(c).decode()} for b, c in store.blocks()]
@@ -901,11 +910,13 @@ class Server:
             if diff:
                 store.set_bulk_attrs(diff)
 
-    def _sync_fragment(self, index, field, view, shard, frag):
-        owners = [n for n in self.cluster.shard_nodes(index, shard) if n.id != self.node.id]
+    def _sync_fragment(self, index, field, view, shard, frag, blocks=None):
+        """``blocks``: the fragment's (block id, checksum) list when the
+        caller already has it from the device."""
+        owners = self._replica_owners(index, shard)
         if not owners:
             return
-        local = dict(frag.blocks())
+        local = dict(blocks if blocks is not None else self.executor.fragment_blocks(index, field, view, shard, frag))
         remote_blocks = {}
         for n in owners:
             try:
@@ -921,7 +932,10 @@ class Server:
             if all(remote_blocks[n.id].get(bid) == local.get(bid) for n in live):
                 continue
             data = [self.client.block_data(n.uri, index, field, view, shard, bid) for n in live]
-            sets, clears = frag.merge_block(bid, data)
+            # the local side of the vote from the arena too; the repair itself is a
+            # host write (it materialises this fragment, which does differ)
+            mine = self.executor.fragment_block_data(index, field, view, shard, bid, frag)
+            sets, clears = frag.merge_block(bid, data, local=mine)
             base = shard * SHARD_WIDTH
             for n, (sr, sc), (cr, cc) in zip(live, sets, clears):
                 if sr:
