@@ -855,17 +855,27 @@ void topn_src(torch::Tensor view, int64_t Q, int64_t S, int64_t K, int64_t H32, 
 }
 
 void bitgemm(torch::Tensor A, torch::Tensor B, int64_t M, int64_t N, int64_t KW, int64_t splits, int64_t mode,
-             torch::Tensor C) {
+             torch::Tensor C, int64_t c_split_stride, bool skip_lower) {
   check_dev(A, "A");
   check_dev(B, "B");
   check_dev(C, "C");
+  TORCH_CHECK(M >= 0 && N >= 0 && KW >= 0 && M < (int64_t(1) << 31) && N < (int64_t(1) << 31), "bitgemm sizes");
   TORCH_CHECK(A.scalar_type() == torch::kInt64 && A.numel() == M * KW, "A int64[M*KW]");
   TORCH_CHECK(B.scalar_type() == torch::kInt64 && B.numel() == N * KW, "B int64[N*KW]");
-  TORCH_CHECK(C.scalar_type() == torch::kInt32 && C.numel() == M * N, "C int32[M*N]");
   TORCH_CHECK(mode >= 0 && mode <= 4, "bitgemm mode");
+  TORCH_CHECK(C.scalar_type() == torch::kInt32 && C.is_contiguous(), "C int32, contiguous");
+  if (c_split_stride == 0) {
+    TORCH_CHECK(C.numel() == M * N, "C int32[M*N]");
+  } else {
+    // one matrix per K-split: every split the launcher runs must land inside C
+    const int64_t ns = pk::bitgemm_splits(KW, int(splits), int(mode));
+    TORCH_CHECK(c_split_stride >= M * N && C.numel() >= (ns - 1) * c_split_stride + M * N,
+                "C must hold one M*N matrix per K-split, c_split_stride apart");
+  }
+  TORCH_CHECK(!skip_lower || (M == N && A.data_ptr() == B.data_ptr()), "skip_lower needs A and B to be the same rows");
   pk::launch_bitgemm(reinterpret_cast<const uint64_t*>(A.data_ptr<int64_t>()),
                      reinterpret_cast<const uint64_t*>(B.data_ptr<int64_t>()), int(M), int(N), KW, int(splits),
-                     int(mode), C.data_ptr<int32_t>(), cur_stream(A));
+                     int(mode), C.data_ptr<int32_t>(), cur_stream(A), c_split_stride, skip_lower);
   check_launch("bitgemm");
 }
 
@@ -1085,7 +1095,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topn_index", &topn_index, "build pass of the device TopN slot index (count or fill)");
   m.def("bsi_minmax_fold", &bsi_minmax_fold, "fold BSI min/max descents into one (value, count, found)");
   m.def("topn_src", &topn_src, "src-filtered TopN over the slot index: mode 1 heap walk, mode 2/3 ids= re-count (rebuilt / kept histograms)");
-  m.def("bitgemm", &bitgemm, "row-pair intersection count matrix of dense bit rows (mode 1 MFMA i8, 0 VALU)");
+  m.def("bitgemm", &bitgemm, "row-pair intersection count matrix of dense bit rows (mode 1 MFMA i8, 0 VALU); "
+        "c_split_stride > 0: one matrix per K-split; skip_lower: no tiles below the diagonal (A is B)",
+        py::arg("A"), py::arg("B"), py::arg("M"), py::arg("N"), py::arg("KW"), py::arg("splits"), py::arg("mode"),
+        py::arg("C"), py::arg("c_split_stride") = 0, py::arg("skip_lower") = false);
   m.def("expr_dense", &expr_dense, "evaluate expressions into dense one-row views (bitmap per shard/key)");
   m.def("shift_dense", &shift_dense, "Shift a dense view by n columns per shard (main + next-shard spill)",
         py::arg("src"), py::arg("S"), py::arg("n"), py::arg("main_out"), py::arg("main_meta"), py::arg("spill_out"),

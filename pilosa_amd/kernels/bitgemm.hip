@@ -19,7 +19,9 @@
 //
 // A workgroup (4 waves, 2x2 wave tiles) owns a 64x64 output tile and one
 // K-split; A/B chunks of 512 bits per row are staged in LDS with coalesced
-// 16-byte loads.  Splits add into C with int32 atomics.
+// 16-byte loads.  Splits add into C with int32 atomics, or (cstride > 0) each
+// into a matrix of its own: with one shard's 16384 words per split that is the
+// per-shard count table of the hot rows (DeviceView.ensure_hot).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -48,7 +50,7 @@ constexpr int KC_BYTES = KC_WORDS * 8;
 template <int MODE>
 __global__ __launch_bounds__(256) void bitgemm_kernel(const uint64_t* __restrict__ A, const uint64_t* __restrict__ B,
                                                       int M, int N, int64_t KW, int64_t kw_per_split,
-                                                      int32_t* __restrict__ C) {
+                                                      int32_t* __restrict__ C, int64_t cstride, int skip_lower) {
   __shared__ uint64_t sa[BT][KC_WORDS];
   __shared__ uint64_t sb[BT][KC_WORDS];
   __shared__ uint64_t tab[256];
@@ -56,6 +58,8 @@ __global__ __launch_bounds__(256) void bitgemm_kernel(const uint64_t* __restrict
   const int tiles_n = (N + BT - 1) / BT;
   const int tile = blockIdx.x;
   const int m0 = (tile / tiles_n) * BT, n0 = (tile % tiles_n) * BT;
+  if (skip_lower && m0 >= n0 + BT) return;   // symmetric C: read at (min, max)
+  C += int64_t(blockIdx.y) * cstride;        // one matrix per K-split (0: all splits add into one)
   const int64_t k0 = int64_t(blockIdx.y) * kw_per_split;
   const int64_t k1 = k0 + kw_per_split < KW ? k0 + kw_per_split : KW;
   if (MODE == 1) {
@@ -139,7 +143,12 @@ __global__ __launch_bounds__(256) void bitgemm_kernel(const uint64_t* __restrict
   for (int i = 0; i < 16; i++) {
     const int m = m0 + wm + (i & 3) + 8 * (i >> 2) + 4 * h, n = n0 + wn + c;
     const int v = MODE >= 1 ? acc[i] : cnt[i];
-    if (m < M && n < N && v) atomicAdd(C + int64_t(m) * N + n, v);
+    if (m < M && n < N) {
+      // a matrix per split has one writer per entry: a plain store, so a
+      // reader never meets a half-summed count and C needs no clearing
+      if (cstride) C[int64_t(m) * N + n] = v;
+      else if (v) atomicAdd(C + int64_t(m) * N + n, v);
+    }
   }
 }
 
@@ -151,12 +160,15 @@ constexpr int BT2 = 128;
 __global__ __launch_bounds__(256) void bitgemm_mfma64_kernel(const uint64_t* __restrict__ A,
                                                              const uint64_t* __restrict__ B, int M, int N,
                                                              int64_t KW, int64_t kw_per_split,
-                                                             int32_t* __restrict__ C) {
+                                                             int32_t* __restrict__ C, int64_t cstride,
+                                                             int skip_lower) {
   __shared__ uint32_t sa[BT2][KC_WORDS * 2 + 1];  // +1 dword: rows on different banks
   __shared__ uint32_t sb[BT2][KC_WORDS * 2 + 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tiles_n = (N + BT2 - 1) / BT2;
   const int m0 = (blockIdx.x / tiles_n) * BT2, n0 = (blockIdx.x % tiles_n) * BT2;
+  if (skip_lower && m0 >= n0 + BT2) return;
+  C += int64_t(blockIdx.y) * cstride;
   const int64_t k0 = int64_t(blockIdx.y) * kw_per_split;
   const int64_t k1 = k0 + kw_per_split < KW ? k0 + kw_per_split : KW;
   const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
@@ -207,7 +219,10 @@ __global__ __launch_bounds__(256) void bitgemm_mfma64_kernel(const uint64_t* __r
       for (int i = 0; i < 16; i++) {
         const int m = m0 + wm + 32 * a + (i & 3) + 8 * (i >> 2) + 4 * h, n = n0 + wn + 32 * b + r;
         const int v = acc[a][b][i];
-        if (m < M && n < N && v) atomicAdd(C + int64_t(m) * N + n, v);
+        if (m < M && n < N) {
+          if (cstride) C[int64_t(m) * N + n] = v;   // one writer per entry: plain store
+          else if (v) atomicAdd(C + int64_t(m) * N + n, v);
+        }
       }
 }
 
@@ -223,13 +238,16 @@ constexpr int K4_WORDS = 32;  // 2048 bits per row per staged chunk
 __global__ __launch_bounds__(256) void bitgemm_kslice_kernel(const uint64_t* __restrict__ A,
                                                              const uint64_t* __restrict__ B, int M, int N,
                                                              int64_t KW, int64_t kw_per_split,
-                                                             int32_t* __restrict__ C) {
+                                                             int32_t* __restrict__ C, int64_t cstride,
+                                                             int skip_lower) {
   __shared__ uint64_t sa[32][K4_WORDS + 1];
   __shared__ uint64_t sb[64][K4_WORDS + 1];
   __shared__ int red[2][16][64];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tiles_n = (N + 63) / 64;
   const int m0 = (blockIdx.x / tiles_n) * 32, n0 = (blockIdx.x % tiles_n) * 64;
+  if (skip_lower && m0 >= n0 + 64) return;
+  C += int64_t(blockIdx.y) * cstride;
   const int64_t k0 = int64_t(blockIdx.y) * kw_per_split;
   const int64_t k1 = k0 + kw_per_split < KW ? k0 + kw_per_split : KW;
   v16i acc[2];
@@ -278,7 +296,12 @@ __global__ __launch_bounds__(256) void bitgemm_kslice_kernel(const uint64_t* __r
     const int b = o >> 10, i = (o >> 6) & 15, l = o & 63;
     const int v = red[b][i][l];
     const int m = m0 + (i & 3) + 8 * (i >> 2) + 4 * (l >> 5), n = n0 + 32 * b + (l & 31);
-    if (m < M && n < N && v) atomicAdd(C + int64_t(m) * N + n, v);
+    if (m < M && n < N) {
+      // a matrix per split has one writer per entry: a plain store, so a
+      // reader never meets a half-summed count and C needs no clearing
+      if (cstride) C[int64_t(m) * N + n] = v;
+      else if (v) atomicAdd(C + int64_t(m) * N + n, v);
+    }
   }
 }
 
@@ -343,27 +366,42 @@ __global__ __launch_bounds__(256) void densify_kernel(ViewDev v, const int64_t* 
 
 }  // namespace
 
-void launch_bitgemm(const uint64_t* A, const uint64_t* B, int M, int N, int64_t KW, int splits, int mode,
-                    int32_t* C, hipStream_t st) {
-  if (M <= 0 || N <= 0 || KW <= 0) return;
-  const int bt = mode == 2 ? BT2 : BT;
-  const int tiles = mode == 4 ? ((M + 31) / 32) * ((N + 63) / 64) : ((M + bt - 1) / bt) * ((N + bt - 1) / bt);
+// chunk-aligned words per K-split and the number of splits that gives
+static int64_t split_words(int64_t KW, int splits, int mode, int* ns) {
   if (splits < 1) splits = 1;
   int64_t per = (KW + splits - 1) / splits;
   const int chunk = mode == 4 ? K4_WORDS : KC_WORDS;
   per = (per + chunk - 1) / chunk * chunk;
-  const int ns = int((KW + per - 1) / per);
+  *ns = int((KW + per - 1) / per);
+  return per;
+}
+
+int bitgemm_splits(int64_t KW, int splits, int mode) {
+  int ns = 0;
+  if (KW > 0) split_words(KW, splits, mode, &ns);
+  return ns;
+}
+
+void launch_bitgemm(const uint64_t* A, const uint64_t* B, int M, int N, int64_t KW, int splits, int mode,
+                    int32_t* C, hipStream_t st, int64_t c_split_stride, bool skip_lower) {
+  if (M <= 0 || N <= 0 || KW <= 0) return;
+  const int bt = mode == 2 ? BT2 : BT;
+  const int tiles = mode == 4 ? ((M + 31) / 32) * ((N + 63) / 64) : ((M + bt - 1) / bt) * ((N + bt - 1) / bt);
+  int ns = 0;
+  const int64_t per = split_words(KW, splits, mode, &ns);
   const dim3 grid(tiles, ns);
+  const int64_t cs = c_split_stride;
+  const int sl = skip_lower ? 1 : 0;
   if (mode == 2)
-    hipLaunchKernelGGL(bitgemm_mfma64_kernel, grid, dim3(256), 0, st, A, B, M, N, KW, per, C);
+    hipLaunchKernelGGL(bitgemm_mfma64_kernel, grid, dim3(256), 0, st, A, B, M, N, KW, per, C, cs, sl);
   else if (mode == 3)
-    hipLaunchKernelGGL(bitgemm_kernel<3>, grid, dim3(256), 0, st, A, B, M, N, KW, per, C);
+    hipLaunchKernelGGL(bitgemm_kernel<3>, grid, dim3(256), 0, st, A, B, M, N, KW, per, C, cs, sl);
   else if (mode == 4)
-    hipLaunchKernelGGL(bitgemm_kslice_kernel, grid, dim3(256), 0, st, A, B, M, N, KW, per, C);
+    hipLaunchKernelGGL(bitgemm_kslice_kernel, grid, dim3(256), 0, st, A, B, M, N, KW, per, C, cs, sl);
   else if (mode == 1)
-    hipLaunchKernelGGL(bitgemm_kernel<1>, grid, dim3(256), 0, st, A, B, M, N, KW, per, C);
+    hipLaunchKernelGGL(bitgemm_kernel<1>, grid, dim3(256), 0, st, A, B, M, N, KW, per, C, cs, sl);
   else
-    hipLaunchKernelGGL(bitgemm_kernel<0>, grid, dim3(256), 0, st, A, B, M, N, KW, per, C);
+    hipLaunchKernelGGL(bitgemm_kernel<0>, grid, dim3(256), 0, st, A, B, M, N, KW, per, C, cs, sl);
 }
 
 void launch_densify(const ViewDev& v, const int64_t* rows, int R, int s0, int s1, uint64_t* out, hipStream_t st) {

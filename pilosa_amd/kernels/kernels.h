@@ -49,8 +49,19 @@ struct ViewDev {
   const uint64_t* twin;
   const int32_t* twin_slot;    // [D]
   int64_t twin_cutoff;
+  // hot-pair table (pair_build): the per-shard intersection counts of the
+  // view's hot_h hottest rows with each other, hot_counts[(s * hot_h + i) *
+  // hot_h + j], read at (min, max) of the two slots: the build skips whole
+  // 128 x 128 tiles strictly below the diagonal (they stay zero), so entries
+  // with i > j exist only inside diagonal tiles (all of them for hot_h <= 128);
+  // hot_slot[d] = slot of dense row d or -1; hot_valid[s] = 0 while shard s's
+  // slice is stale.  nullptr / 0 = no table
+  const int32_t* hot_counts;
+  const int32_t* hot_slot;     // [D]
+  const uint8_t* hot_valid;    // [S]
+  int64_t hot_h;
 };
-static_assert(sizeof(ViewDev) == 88, "ViewDev layout");
+static_assert(sizeof(ViewDev) == 120, "ViewDev layout");
 
 struct BsiArgs {
   int32_t view;
@@ -69,6 +80,8 @@ void launch_expr_materialize(const QueryProg* progs, int Q, const ViewDev* views
 // out[ti[q]] += sum over the U rows of partial[U][n] (pair-kernel partials)
 void launch_partial_sum_scatter(const int32_t* partial, int64_t U, int n, const int64_t* ti, int64_t* out,
                                 int64_t nout, hipStream_t st);
+// A query whose two rows both have a slot in their view's hot-pair table is
+// answered by pair_build from the table (shipped variants 6 / 39 / 63 only).
 void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int S, uint2* pairs, int32_t* partial,
                        int cq, int variant, hipStream_t st);
 // BSI predicate -> one bitmap container per (shard, key): payload u16[S*16*4096], meta int64[S*16].
@@ -175,8 +188,16 @@ void launch_topn_hot_meta(const ViewDev& v, int S, int K, int R, const int32_t* 
 // Row-pair intersection count matrix C[M][N] (int32, atomically accumulated)
 // of dense bit rows A[M][KW] and B[N][KW] (u64 words), bitgemm.hip.
 // mode 1: i8 MFMA (v_mfma_i32_32x32x32_i8), mode 0: VALU popcount.
+// c_split_stride > 0: K-split y adds into C + y * c_split_stride instead (one
+// matrix per split; with KW / splits = 16384 words of densify output, one per
+// shard).  skip_lower: tiles strictly below the diagonal are not computed
+// (A and B the same rows: C is symmetric, read it at (min, max)).  With a
+// split stride every entry of a computed tile is stored, not added (C needs no
+// clearing; skipped tiles are left as they are).
 void launch_bitgemm(const uint64_t* A, const uint64_t* B, int M, int N, int64_t KW, int splits, int mode,
-                    int32_t* C, hipStream_t st);
+                    int32_t* C, hipStream_t st, int64_t c_split_stride = 0, bool skip_lower = false);
+// K-splits launch_bitgemm runs for these arguments (rows of a per-split C).
+int bitgemm_splits(int64_t KW, int splits, int mode);
 // Dense bit rows of an arena: out[R][(s1-s0) * 16384] u64 for dense rows `rows`.
 void launch_densify(const ViewDev& v, const int64_t* rows, int R, int s0, int s1, uint64_t* out, hipStream_t st);
 

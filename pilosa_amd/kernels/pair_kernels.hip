@@ -62,6 +62,23 @@
 // SLOWER, 16.73 vs 16.30 ms alone and 15.42 vs 15.05 ms on top of the twins
 // (8 predicated, conflicting ds_write_b32 and 8 more VGPRs against 8 b128
 // stores): built into the kbench module only.
+// Hot-pair table (profiles/hot_pairs/): six rounds inside the kernel left half
+// of its time as fixed per-pair cost, so the lever is the number of pairs.
+// Rows are queried by the Zipf law that fills them: most queries name two hot
+// rows, whose per-shard intersection counts change only when they are written.
+// Each view keeps int32 hot_counts[S][H][H] for its H = 512 rows of most bits
+// (DeviceView.ensure_hot: densify + the MFMA bitgemm with one K-split per
+// shard, 0.47 s and 954 MiB on the headline index; a written shard's slice is
+// masked out by hot_valid[s] until it is recomputed).  pair_build answers a
+// query whose two rows both have a slot from the table: key 0's entry carries
+// {PRECOUNTED, count}, keys 1-15 NONE, no metas are loaded; the pair kernel's
+// prologue copies the count into its partial (one compare; registers and
+// occupancy unchanged).  kbench, min of 10, variant 63 alternated three times:
+// no table 15.12-15.15 ms (this module with the table off, not the parent's
+// build, whose own record for the kernel is 15.05 ms); H = 128 / 256 / 512:
+// 9.95 / 8.08 / 6.46 ms with 28 / 44 / 59 % of the (shard, query) entries
+// precounted.  The precounted queries
+// still occupy their lanes of the grid (compaction: a later change).
 //
 // Reference hot loops replaced: roaring/roaring.go:3078-3215 intersectionCount*
 // and executor.go:1230-1290 (executeCount over executeIntersect).
@@ -74,6 +91,11 @@ namespace pk {
 namespace {
 
 constexpr uint32_t NONE = 0xffffffffu;
+// pairs entry of a query pair_build answered from the view's hot-pair table:
+// x = PRECOUNTED, y = the shard's count (key 0's entry; keys 1-15 hold NONE).
+// Container indices stay below it (the engine takes the pair path only for
+// views of fewer than 0xffffffff containers).
+constexpr uint32_t PRECOUNTED = 0xfffffffeu;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
@@ -141,16 +163,32 @@ __global__ __launch_bounds__(256) void keymask_build_kernel(ViewDev v, int S, ui
 
 __global__ __launch_bounds__(256) void pair_build_kernel(const QueryProg* __restrict__ progs, int Q,
                                                          const ViewDev* __restrict__ views, int S,
-                                                         uint2* __restrict__ pairs) {
+                                                         uint2* __restrict__ pairs, int hot) {
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= int64_t(Q) * S) return;
   const int s = int(t / Q), q = int(t % Q);
   const QueryProg& qp = progs[q];
+  uint2* dst = pairs + int64_t(s) * 16 * Q + q;
+  // hot-pair table: both rows are hot rows of one view whose slice of this
+  // shard is valid -> the shard's count rides in key 0's entry, no metas
+  if (hot && qp.leaf_view[0] == qp.leaf_view[1] && qp.leaf_row[0] >= 0 && qp.leaf_row[1] >= 0) {
+    const ViewDev& hv = views[qp.leaf_view[0]];
+    if (hv.hot_counts != nullptr && gp(hv.hot_valid)[s]) {
+      const int sa = gp(hv.hot_slot)[qp.leaf_row[0]], sb = gp(hv.hot_slot)[qp.leaf_row[1]];
+      if (sa >= 0 && sb >= 0) {
+        const int64_t h = hv.hot_h;
+        const uint32_t c = uint32_t(gp(hv.hot_counts)[(int64_t(s) * h + min(sa, sb)) * h + max(sa, sb)]);
+        dst[0] = make_uint2(PRECOUNTED, c);
+#pragma unroll
+        for (int j = 1; j < 16; j++) dst[int64_t(j) * Q] = make_uint2(NONE, NONE);
+        return;
+      }
+    }
+  }
   int64_t loa, lob;
   const uint32_t pa = row_keys(views[qp.leaf_view[0]], s, qp.leaf_row[0], loa);
   const uint32_t pb = row_keys(views[qp.leaf_view[1]], s, qp.leaf_row[1], lob);
   const uint32_t both = pa & pb;
-  uint2* dst = pairs + int64_t(s) * 16 * Q + q;
 #pragma unroll
   for (int j = 0; j < 16; j++) {
     uint2 e = make_uint2(NONE, NONE);
@@ -801,9 +839,12 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
   int64_t ma = 0, mb = 0;
   uint64_t pal = 0, pbl = 0;
   uint64_t sha = 0;   // SHD: A's bitmap shadow for this unit (0 = none)
+  int mine = 0;
   if (lane < nq) {
     const uint2 e = pairs[u * Q + q0 + lane];
-    if (e.x != NONE) {
+    if (e.x == PRECOUNTED) {
+      mine = int(e.y);   // answered by pair_build from the hot-pair table
+    } else if (e.x != NONE) {
       ea = e.x;
       vai = progs[q0 + lane].leaf_view[0];
       const int vbi = progs[q0 + lane].leaf_view[1];
@@ -820,8 +861,7 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
     }
   }
   uint64_t todo = __ballot(ea != NONE);
-  int mine = 0;
-  if (DBG) lb[lane] = 0;   // cost-attribution variants keep v6's 8 KiB LDS (and occupancy)
+  if (DBG) lb[lane] = 0;  // cost-attribution variants keep v6's 8 KiB LDS (and occupancy)
   if (todo) {
     uint32_t cached = NONE;
     int cached_v = -1;
@@ -1288,8 +1328,13 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
                        int cq, int variant, hipStream_t st) {
   const int64_t items = int64_t(Q) * S;
   if (items == 0) return;
-  hipLaunchKernelGGL(pair_build_kernel, dim3(unsigned((items + 255) / 256)), dim3(256), 0, st, progs, Q, views, S,
-                     pairs);
+  // pair_build runs once the variant is settled: only the shipped kernels
+  // (plain v6, its serving variant 39, the twin variant 63) are handed
+  // entries answered from the hot-pair table
+  auto build = [&](bool hot) {
+    hipLaunchKernelGGL(pair_build_kernel, dim3(unsigned((items + 255) / 256)), dim3(256), 0, st, progs, Q, views, S,
+                       pairs, hot ? 1 : 0);
+  };
   const int64_t units = int64_t(S) * 16;
   // bitmap twins / un-staging: v6 at 64 queries per wave only -- 61 twinned A,
   // 62 twinned B, 63 both (shipped), 64 un-staging, 65 both twins +
@@ -1301,6 +1346,7 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
       variant = 6;
     } else {
       const int64_t wv = units * ((Q + 63) / 64);
+      build(variant == 63);
       switch (variant) {
 #ifdef PK_KBENCH
         case 61: launch_v6_twn<1, false>(wv, progs, Q, views, S, pairs, partial, st); break;
@@ -1331,6 +1377,7 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
 #endif
   if (variant == 41 && cq <= 0 && Q <= 128) variant = 42;   // the same with dense shadows
   if (cq <= 0) cq = Q <= 128 ? 8 : (Q <= 2048 ? 32 : 64);
+  build(variant == 6 || variant == 39);
 // The shipped build instantiates v6, its serving variant 39 and (above) the
 // bitmap-twin variant 63 only; every
 // measured-and-rejected variant and cost-isolation skeleton (v10-v13,

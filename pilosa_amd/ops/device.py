@@ -12,6 +12,7 @@ of one view).  ``Expr`` trees are compiled here.
 """
 from __future__ import annotations
 
+import math
 import os
 import threading
 import time
@@ -49,12 +50,14 @@ QPROG_DTYPE = np.dtype([("nleaf", "<i4"), ("nprog", "<i4"), ("leaf_view", "<i4",
                         ("leaf_row", "<i8", (MAXLEAF,)), ("prog", "u1", (MAXPROG,)), ("pad", "<i8", (3,))])
 VIEWDEV_DTYPE = np.dtype([("rowptr", "<u8"), ("shard_base", "<u8"), ("meta", "<u8"), ("payload", "<u8"),
                           ("D", "<i8"), ("keymask", "<u8"), ("shadow", "<u8"), ("shadow_slot", "<u8"),
-                          ("twin", "<u8"), ("twin_slot", "<u8"), ("twin_cutoff", "<i8")])
-assert QPROG_DTYPE.itemsize == 256 and VIEWDEV_DTYPE.itemsize == 88
+                          ("twin", "<u8"), ("twin_slot", "<u8"), ("twin_cutoff", "<i8"),
+                          ("hot_counts", "<u8"), ("hot_slot", "<u8"), ("hot_valid", "<u8"), ("hot_h", "<i8")])
+assert QPROG_DTYPE.itemsize == 256 and VIEWDEV_DTYPE.itemsize == 120
 
 _ext = None
 _ext_lock = threading.Lock()
 _twin_lock = threading.Lock()
+_hot_lock = threading.Lock()
 _D2H_POLL = float(os.environ.get("PILOSA_D2H_POLL", "0"))
 
 
@@ -372,8 +375,8 @@ class DeviceView:
         self._rowptr_host[si] = rp_new
         self.payload_used += npay
         self.garbage_u16 += npay
+        self.shard_gen[si] += 1   # before generation: who sees the new generation sees the written shard
         self.generation += 1
-        self.shard_gen[si] += 1
         return True
 
     def update_shard(self, si: int, bitmap) -> bool:
@@ -423,8 +426,8 @@ class DeviceView:
                 torch.from_numpy(pay_s[:npay].view(np.int16)).to(dev))
         self.payload_used += npay
         self.garbage_u16 += npay  # approximate: the shard's previous payload is now unreachable
+        self.shard_gen[si] += 1   # before generation: who sees the new generation sees the written shard
         self.generation += 1
-        self.shard_gen[si] += 1
         return True
 
     # ------------------------------------------------------------ growth
@@ -767,9 +770,9 @@ class DeviceView:
             self._rowptr_host[si] = rp_new
         if scatter_at:
             self._flush_meta_scatter(scatter_at, scatter_val)
-        self.generation += 1
-        for jb in jobs:
+        for jb in jobs:     # before generation, as above
             self.shard_gen[jb[0]] += 1
+        self.generation += 1
         return failed
 
     def _flush_meta_scatter(self, at, val):
@@ -860,6 +863,9 @@ class DeviceView:
                                                        self.t_payload))
         for sh in (getattr(self, "_shadow", None), getattr(self, "_twin", None)):
             n += sh[1].numel() * 8 + sh[2].numel() * 4 if sh is not None else 0
+        hp = getattr(self, "_hot", None)
+        if hp is not None:
+            n += hp.counts.numel() * 4 + hp.slot.numel() * 4 + hp.valid.numel()
         return n
 
     def dense(self, row: int) -> int:
@@ -879,7 +885,7 @@ class DeviceView:
         ok = (self.D > 0) & (self.rows[i] == rows) if self.D else np.zeros(len(rows), bool)
         return np.where(ok, i, -1).astype(np.int64)
 
-    def viewdev(self) -> np.void:
+    def viewdev(self, hot: bool = True) -> np.void:
         rec = np.zeros((), dtype=VIEWDEV_DTYPE)
         rec["rowptr"] = self.t_rowptr.data_ptr()
         rec["shard_base"] = self.t_shard_base.data_ptr()
@@ -898,6 +904,12 @@ class DeviceView:
             rec["twin"] = tw[1].data_ptr()
             rec["twin_slot"] = tw[2].data_ptr()
             rec["twin_cutoff"] = tw[5]
+        hp = getattr(self, "_hot", None)
+        if hot and hp is not None and self.hot_fresh():
+            rec["hot_counts"] = hp.counts.data_ptr()
+            rec["hot_slot"] = hp.slot.data_ptr()
+            rec["hot_valid"] = hp.valid.data_ptr()
+            rec["hot_h"] = hp.h
         return rec
 
     def shadow_fresh(self) -> bool:
@@ -1054,6 +1066,162 @@ class DeviceView:
         self._twin = (self.generation, buf, slot, now, rows, cutoff)
         return True
 
+    # hot-pair table (pair_kernels.hip pair_build): per shard the intersection
+    # counts of the HOTPAIR_ROWS rows with the most bits with each other,
+    # int32[S][H][H], so a Count(Intersect) of two hot rows costs one lookup
+    # per shard instead of up to 16 container pairs.  H is capped by a quarter
+    # of free HBM; views of fewer than HOTPAIR_MIN_CONTAINERS containers carry
+    # none (nothing to gain, and a build per view generation to lose).
+    HOTPAIR_ROWS = int(os.environ.get("PILOSA_HOTPAIR_ROWS", "512"))
+    HOTPAIR_MIN_CONTAINERS = int(os.environ.get("PILOSA_HOTPAIR_MIN_CONTAINERS", "65536"))
+    HOTPAIR_MIN_INTERVAL_S = 30.0          # full builds and refreshes of written shards
+    # written shards recomputed inside the request that finds them.  0: they
+    # are masked out (hot_valid) and recomputed on the interval, as the twins
+    # are: recomputing one shard's slice (densify of H rows + its bitgemm
+    # tiles + a stream synchronise) costs about as much as a whole
+    # serving-size batch (profiles/hot_pairs/README.md, one-off costs)
+    HOTPAIR_REFRESH_SHARDS = int(os.environ.get("PILOSA_HOTPAIR_REFRESH_SHARDS", "0"))
+    HOTPAIR_FULL_RUNS = 48                 # more runs of written shards than this: recompute every shard
+    HOTPAIR_SCRATCH_BYTES = 3 << 29        # dense rows of one block of shards (1.5 GiB)
+
+    def hot_fresh(self) -> bool:
+        """Whether the hot-pair table would be passed to the kernels now."""
+        hp = getattr(self, "_hot", None)
+        return hp is not None and hot_table_passable(hp.rows_gen, hp.gen, self.rows_gen, self.generation) and \
+            not len(hot_stale_shards(hp.shard_gen, self.shard_gen))
+
+    def ensure_hot(self) -> bool:
+        """Build the hot-pair table or bring it up to this view generation.
+
+        The table is keyed on dense row indices, so a changed ``rows_gen``
+        drops it (rebuilt at most every HOTPAIR_MIN_INTERVAL_S, as the twins
+        are).  A changed ``shard_gen[si]`` clears ``hot_valid[si]`` on the
+        device before anything else is launched; the slice is recomputed
+        once HOTPAIR_MIN_INTERVAL_S has passed since the last build or
+        refresh (up to HOTPAIR_REFRESH_SHARDS slices right away, none by
+        default).  :meth:`viewdev` passes the table only while it was
+        synchronised at the current generation and shard generations, so no
+        stale slice is ever readable and answers never depend on the table.
+        Returns whether it is passed."""
+        if self.HOTPAIR_ROWS <= 0 or self.device.type != "cuda" or not self.S or not self.D or \
+                self.container_count < self.HOTPAIR_MIN_CONTAINERS:
+            return False
+        hp = getattr(self, "_hot", None)
+        if hp is not None and self.hot_fresh() and not hp.pending.any():
+            return True
+        with _hot_lock:   # request threads: one build, the others find it done
+            return self._sync_hot()
+
+    def _sync_hot(self) -> bool:
+        import time
+
+        import torch
+
+        hp = getattr(self, "_hot", None)
+        now = time.monotonic()
+        if hp is not None and hp.rows_gen == self.rows_gen:
+            gen = self.generation
+            shard_gen = self.shard_gen.copy()
+            stale = hot_stale_shards(hp.shard_gen, shard_gen)
+            if len(stale):
+                # ordered before every later kernel of this stream; other
+                # streams wait for the synchronize below (gen is not yet current)
+                hp.valid[torch.from_numpy(stale).to(self.device)] = 0
+                hp.pending[stale] = True
+                self.hot_stats["invalidated_shards"] += len(stale)
+            todo = np.flatnonzero(hp.pending)
+            filled = False
+            if len(todo) and (len(todo) <= self.HOTPAIR_REFRESH_SHARDS or
+                              now - hp.built >= self.HOTPAIR_MIN_INTERVAL_S):
+                filled = True
+                # a launch per run of consecutive shards: past HOTPAIR_FULL_RUNS runs the
+                # whole table is cheaper (6.5 ms a run against 0.46 s for 954 shards)
+                if len(shard_runs(todo, self.S)) > self.HOTPAIR_FULL_RUNS:
+                    todo = np.arange(self.S)
+                try:
+                    self._hot_fill(hp, todo)
+                except torch.cuda.OutOfMemoryError:
+                    # no room for the scratch now: the slices stay masked (and pending) until the next interval
+                    hp.built = now
+                else:
+                    hp.pending[todo] = False
+                    hp.built = now
+                    self.hot_stats["refreshed_shards"] += len(todo)
+            if len(stale) or filled:   # valid was written or a fill ran; else nothing was launched
+                torch.cuda.current_stream(self.device).synchronize()
+            hp.shard_gen = shard_gen
+            hp.gen = gen
+            return gen == self.generation
+        if hp is not None and now - hp.built < self.HOTPAIR_MIN_INTERVAL_S:
+            return False
+        if hp is None and getattr(self, "_hot_declined", None) == self.generation:
+            return False
+        self._hot = hp = None   # the old table's HBM is free for the new one
+        free, _ = torch.cuda.mem_get_info(self.device)
+        # the build's scratch comes on top of the table
+        H = hot_table_rows(self.HOTPAIR_ROWS, self.D, self.S, max(0, free - self.HOTPAIR_SCRATCH_BYTES))
+        rows = self._hot_dense_rows(H) if H >= 2 else np.zeros(0, np.int32)
+        if len(rows) < 2:
+            self._hot_declined = self.generation
+            return False
+        H = len(rows)
+        hp = _HotPairs()
+        hp.h, hp.rows = H, rows
+        hp.rows_gen, hp.gen, hp.shard_gen = self.rows_gen, self.generation, self.shard_gen.copy()
+        slot = torch.full((self.D,), -1, dtype=torch.int32)
+        slot[torch.from_numpy(rows.astype(np.int64))] = torch.arange(H, dtype=torch.int32)
+        hp.pending = np.zeros(self.S, bool)
+        try:
+            hp.slot = slot.to(self.device)
+            hp.rows_t = torch.from_numpy(rows.astype(np.int64)).to(self.device)
+            # zeros: the tiles below the diagonal are never written
+            hp.counts = torch.zeros((self.S, H, H), dtype=torch.int32, device=self.device)
+            hp.valid = torch.zeros(self.S, dtype=torch.uint8, device=self.device)
+            self._hot_fill(hp, np.arange(self.S))
+        except torch.cuda.OutOfMemoryError:
+            del hp      # a request declines the table, it does not fail on it
+            self._hot_declined = self.generation
+            return False
+        # readers on any stream see a complete table
+        torch.cuda.current_stream(self.device).synchronize()
+        hp.built = time.monotonic()
+        self.hot_stats["full_builds"] += 1
+        self._hot = hp
+        return hp.gen == self.generation
+
+    @property
+    def hot_stats(self) -> dict:
+        """Counters of the hot-pair table: full builds, shard slices
+        invalidated by writes, shard slices recomputed."""
+        st = self.__dict__.get("_hot_stats")
+        if st is None:
+            st = self.__dict__["_hot_stats"] = {"full_builds": 0, "invalidated_shards": 0, "refreshed_shards": 0}
+        return st
+
+    def _hot_fill(self, hp, shards: np.ndarray) -> None:
+        """hot_counts[s] of the given shards (ascending), then hot_valid[s] =
+        1: per block of consecutive shards the hot rows are densified into
+        scratch and one bitgemm launch, one K-split per shard, writes the
+        block's count matrices (tiles below the diagonal skipped)."""
+        import torch
+
+        ext = kernels()
+        H = hp.h
+        rows_t = hp.rows_t
+        vd = self.viewdev_tensor()
+        per_shard = H * 16384 * 8
+        block = max(1, int(self.HOTPAIR_SCRATCH_BYTES // per_shard))
+        for s0, s1 in shard_runs(shards, block):
+            ns = s1 - s0
+            scratch = torch.empty(H * ns * 16384, dtype=torch.int64, device=self.device)
+            ext.densify(vd, rows_t, s0, s1, scratch)
+            out = hp.counts[s0:s1]
+            # every entry of a computed tile is stored: no clearing, and a batch in
+            # flight on another stream reads the old or the new count, never a partial sum
+            ext.bitgemm(scratch, scratch, H, H, ns * 16384, ns, 2, out.view(-1), H * H, True)
+            hp.valid[s0:s1] = 1
+            del scratch
+
     def viewdev_tensor(self):
         """The ViewDev record as the uint8 host tensor the kernel bindings take."""
         import torch
@@ -1134,6 +1302,49 @@ def select_twin_rows(sample, D: int, cutoff: int, max_rows: int) -> np.ndarray:
     return np.sort(idx).astype(np.int32)
 
 
+class _HotPairs:
+    """State of a view's hot-pair table (DeviceView.ensure_hot): device
+    tensors counts int32[S, h, h], slot int32[D], valid uint8[S]; the dense
+    rows behind the slots; the rows_gen / generation / shard_gen it was last
+    synchronised at; pending[s] = shard s's slice awaits a refresh."""
+
+    __slots__ = ("h", "rows", "rows_t", "counts", "slot", "valid", "rows_gen", "gen", "shard_gen", "pending", "built")
+
+
+def hot_table_rows(want: int, D: int, S: int, free_bytes: int) -> int:
+    """Rows of a hot-pair table: at most ``want`` and D, and int32[S][H][H]
+    within a quarter of the free device memory."""
+    if want <= 0 or D <= 0 or S <= 0:
+        return 0
+    cap = math.isqrt(max(int(free_bytes), 0) // 4 // (4 * S))
+    return max(0, min(int(want), int(D), cap))
+
+
+def hot_table_passable(table_rows_gen: int, table_gen: int, rows_gen: int, generation: int) -> bool:
+    """A hot-pair table may be read only by batches of the view generation it
+    was last synchronised at (every write bumps the generation: its shards'
+    slices are invalidated or refreshed first) and only while the dense row
+    directory it indexes is unchanged."""
+    return table_rows_gen == rows_gen and table_gen == generation
+
+
+def hot_stale_shards(snapshot: np.ndarray, shard_gen: np.ndarray) -> np.ndarray:
+    """Shards written since ``snapshot`` of shard_gen was taken (ascending)."""
+    return np.flatnonzero(np.asarray(snapshot) != np.asarray(shard_gen)).astype(np.int64)
+
+
+def shard_runs(shards, block: int):
+    """Ascending shard indices -> [(s0, s1)] runs of consecutive shards, each
+    at most ``block`` long."""
+    out = []
+    for s in np.asarray(shards, np.int64).tolist():
+        if out and out[-1][1] == s and s - out[-1][0] < block:
+            out[-1][1] = s + 1
+        else:
+            out.append([s, s + 1])
+    return [(a, b) for a, b in out]
+
+
 # ---------------------------------------------------------------- engine
 
 class DeviceRowBlock:
@@ -1182,6 +1393,10 @@ class GpuEngine:
         built = set(getattr(kernels(), "PAIR_VARIANTS", ()))
         self.use_twin = os.environ.get("PILOSA_TWIN", "1") != "0" and 63 in built
         self.use_unstage = os.environ.get("PILOSA_UNSTAGE", "0") != "0" and {64, 65} <= built
+        # Count(Intersect) of two hot rows of a view is looked up in the view's
+        # per-shard hot-pair table by pair_build (DeviceView.ensure_hot); the
+        # launcher hands it to the shipped kernels only (v6, 39, 63)
+        self.use_hot = os.environ.get("PILOSA_HOTPAIR", "1") != "0"
         # Count(Union(leaves)) route: union_count_kernel (bitmap_kernels.hip)
         self.use_union = os.environ.get("PILOSA_UNION_KERNEL", "1") != "0"
         # 2 = union_count2_kernel (flat chunk walk, parallel meta fetch), 1 = union_count_kernel
@@ -1192,6 +1407,9 @@ class GpuEngine:
         a view carries dense shadows, 2 = a view carries fresh bitmap twins, 0
         = neither.  Twins are ensured only for batches that run the
         64-queries-per-wave pair kernel."""
+        if self.use_hot and self.and2_variant in (6, 39, 63):   # any batch size
+            for v in views:
+                v.ensure_hot()
         if self.use_shadow and any([v.ensure_shadow() for v in views]):
             return 1
         wave64 = self.and2_cq == 64 or (self.and2_cq <= 0 and n > 2048)
@@ -1203,7 +1421,7 @@ class GpuEngine:
     def _views_tensor(self, views: List["DeviceView"]):
         arr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
         for i, v in enumerate(views):
-            arr[i] = v.viewdev()
+            arr[i] = v.viewdev(hot=self.use_hot)
         # the same view table (same arenas, same buffers) is uploaded once:
         # a BSI / single-view request otherwise pays one H2D for it per call
         key = arr.tobytes()
@@ -1339,7 +1557,7 @@ class GpuEngine:
         shd = self._and2_aux(views, int(is_and2.sum())) if is_and2.any() else 0
         varr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
         for i, v in enumerate(views):
-            varr[i] = v.viewdev()
+            varr[i] = v.viewdev(hot=self.use_hot)
         host = [varr.view(np.uint8)]
         meta = []
         for k in (KIND_AND2, KIND_ROW, KIND_FLAT, KIND_UNION, KIND_GENERIC):
@@ -1372,7 +1590,7 @@ class GpuEngine:
             shd = self._and2_aux(views, n_and2)
         varr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
         for i, v in enumerate(views):
-            varr[i] = v.viewdev()
+            varr[i] = v.viewdev(hot=self.use_hot)
         tv, tb = self._h2d_many([varr.view(np.uint8), buf])
         parts = []
         for kind, n, po, oo in segs:
@@ -1529,11 +1747,15 @@ class GpuEngine:
             return torch.from_numpy(z) if as_tensor else z
         progs = _canonical_and2(progs)
         np_, pg = progs["nprog"], progs["prog"]
+        and2 = self.use_and2 and max(v.container_count for v in views) < 0xFFFFFFFF and \
+            bool(np.all((np_ == 3) & (pg[:, 0] == 0) & (pg[:, 1] == 1) & (pg[:, 2] == OP_AND)))
+        if and2 and self.use_hot and self.and2_variant in (6, 39, 63):
+            for v in views:
+                v.ensure_hot()
         varr = np.zeros(len(views), dtype=VIEWDEV_DTYPE)
         for i, v in enumerate(views):
-            varr[i] = v.viewdev()
-        if self.use_and2 and max(v.container_count for v in views) < 0xFFFFFFFF and \
-                bool(np.all((np_ == 3) & (pg[:, 0] == 0) & (pg[:, 1] == 1) & (pg[:, 2] == OP_AND))):
+            varr[i] = v.viewdev(hot=self.use_hot)
+        if and2:
             progs = self._hot_leaf_first(progs, np.ones(Q, bool))
             lr = progs["leaf_row"]
             order = np.lexsort((lr[:, 1], lr[:, 0]))

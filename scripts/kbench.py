@@ -7,7 +7,10 @@ Pair-kernel variant ids of the bitmap twins / un-staging (64 queries per
 wave): 61 twinned A only, 62 twinned B only, 63 both, 64 un-staging only, 65
 both twins + un-staging; --twin-cutoff lists the cutoffs T each twin variant
 is timed at (the twin is rebuilt per T).  6 = the plain v6 kernel; a variant
-may be listed several times to alternate it with others."""
+may be listed several times to alternate it with others.  --hot-rows times
+the shipped kernels with the hot-pair table of H rows (DeviceView.ensure_hot)
+next to H = 0 on the same arena, and prints how many entries it answers.
+PILOSA_HIPKERNELS=_hipkernels runs the shipped module (variants 6 and 63)."""
 import argparse
 import json
 import math
@@ -36,6 +39,8 @@ def main():
     ap.add_argument("--variants", default="", help="extra kernel variants at --cq's first size, e.g. 4,5 (38@8: at 8 queries per wave)")
     ap.add_argument("--twin-cutoff", default="", help="twin cutoffs T for variants 61/62/63/65, e.g. 3072,2730,2048 "
                     "(default: DeviceView.TWIN_CUTOFF)")
+    ap.add_argument("--hot-rows", default="", help="hot-pair table sizes H each --variants setting of the shipped "
+                    "kernels (6, 39, 63) is timed at, e.g. 0,128,256,512 (0 = no table; default: no table)")
     args = ap.parse_args()
     import torch
 
@@ -63,14 +68,17 @@ def main():
         vv, _, cq = v.partition("@")   # "38@8": variant 38 at 8 queries per wave
         cq = int(cq) if cq else cq0
         cuts = [int(t) for t in args.twin_cutoff.split(",") if t] if int(vv) in (61, 62, 63, 65) else []
+        hots = [int(h) for h in args.hot_rows.split(",") if h] if int(vv) in (6, 39, 63) else []
         for t in cuts or [None]:
-            name = f"and2var{vv}_cq{cq}" + (f"_t{t}" if t is not None else "")
-            while name in [c[0] for c in configs]:
-                name += "'"      # a repeat of the same setting (alternating runs)
-            configs.append((name, {"and2_cq": cq, "and2_variant": int(vv), "twin_cutoff": t}))
+            for hr in hots or [0]:
+                name = f"and2var{vv}_cq{cq}" + (f"_t{t}" if t is not None else "") + (f"_h{hr}" if hr else "")
+                while name in [c[0] for c in configs]:
+                    name += "'"      # a repeat of the same setting (alternating runs)
+                configs.append((name, {"and2_cq": cq, "and2_variant": int(vv), "twin_cutoff": t, "hot_rows": hr}))
     for name, cfg in configs:
         eng = GpuEngine(dev)
         cut = cfg.pop("twin_cutoff", None)
+        hot = cfg.pop("hot_rows", 0)
         for k, v in cfg.items():
             setattr(eng, k, v)
         eng.use_unstage = eng.use_twin = False      # variants are explicit here: 6 is the plain kernel
@@ -78,8 +86,29 @@ def main():
         if cut is not None and (view.TWIN_CUTOFF != cut or not view.twin_fresh()):
             view._twin = None        # rebuilt at this cutoff by prepare_progs
             view.TWIN_CUTOFF = cut
+        eng.use_hot = hot > 0        # the table is explicit too
+        if hot and (view.HOTPAIR_ROWS != hot or getattr(view, "_hot", None) is None):
+            view._hot = None         # rebuilt at this size by prepare_progs
+            view.HOTPAIR_ROWS = hot
+            view.HOTPAIR_MIN_CONTAINERS = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            view.ensure_hot()
+            hp = view._hot
+            if hp is not None:
+                print(f"hot-pair table H={hp.h}: {hp.counts.numel() * 4 / 2**20:.0f} MiB, "
+                      f"build {time.perf_counter() - t0:.3f} s", flush=True)
         t0 = time.perf_counter()
         h = eng.prepare_progs(progs, views, S)
+        if hot:
+            # how much of the batch the table answers: marked entries of the pairs buffer
+            (tp, _, _, n), = h[3]
+            pr = torch.empty(S * 16 * n * 2, dtype=torch.int32, device=dev)
+            pt = torch.empty(S * 16 * n, dtype=torch.int32, device=dev)
+            eng.ext.and2_count(tp, h[2], S, pr, pt, eng.and2_cq, cfg["and2_variant"])
+            marked = int((pr.view(-1, 2)[:, 0] == -2).sum().item())
+            print(f"{name}: {marked} of {S * n} (shard, query) entries precounted ({marked / (S * n):.1%})", flush=True)
+            del pr, pt
         if cut is not None and view.twin_fresh():
             tw = view._twin
             print(f"twin T={cut}: {len(tw[4])} rows, {tw[1].numel() * 8 / 2**30:.2f} GiB, "

@@ -7,7 +7,13 @@ Also: LDS probes (one per array B value) per B size class, array stagings per
 A size class, and the pairs / probes / stagings whose A or B container a
 bitmap twin at cutoff T would replace (rows picked by select_twin_rows over
 the sampled shards, containers by n > T) with the bytes that adds.
-Usage: python scripts/pair_stats.py [--sample 2] [--batch 4096] [--twin-cutoff 3072,2730,2048]"""
+Hot-pair table (--hot-rows H,...): with the H rows of most bits answered
+from the per-shard count table whenever both rows of a query are among them,
+what remains in the pair kernel as a share of today -- queries answered,
+pairs, array probes, bitmap / twin B pairs, stagings, referenced bytes (twins
+at --hot-twin-cutoff, the planner's dedupe ignored).
+Usage: python scripts/pair_stats.py [--sample 2] [--batch 4096] [--twin-cutoff 3072,2730,2048]
+       [--hot-rows 64,128,256,512,1024] [--seed 1234]"""
 import argparse
 import collections
 import json
@@ -26,6 +32,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--cq", type=int, default=64)
     ap.add_argument("--twin-cutoff", default="3072,2730,2048")
+    ap.add_argument("--hot-rows", default="64,128,256,512,1024")
+    ap.add_argument("--hot-twin-cutoff", type=int, default=2048)
+    ap.add_argument("--seed", type=int, default=1234)
     args = ap.parse_args()
     from pilosa_amd import _roaring
     from pilosa_amd.ops.device import select_twin_rows
@@ -38,7 +47,7 @@ def main():
     typ = (meta >> 4) & 3
     n = (meta >> 6) & 0x1FFFF
     jj = meta & 15
-    rng = np.random.default_rng(1234)
+    rng = np.random.default_rng(args.seed)
     ra, rb = zipf_rows(rng, args.batch), zipf_rows(rng, args.batch)
     keys = np.concatenate([ra, rb])
     u, inv, cnt = np.unique(keys, return_inverse=True, return_counts=True)
@@ -61,6 +70,20 @@ def main():
     stage_cls = collections.Counter()     # array A stagings per size class
     tw = {t: collections.Counter() for t in cuts}
     ref_bytes = 0                         # bytes the kernel references (A per staging, B per pair)
+    # hot-pair table: the H dense rows with the most bits over the sample
+    hots = [int(h) for h in args.hot_rows.split(",") if h]
+    bits = np.zeros(D, np.int64)
+    for s in range(args.sample):
+        bits += np.bincount(np.repeat(np.arange(D), np.diff(rp[s])), weights=n[sb[s]:sb[s] + rp[s, -1]],
+                            minlength=D).astype(np.int64)
+    by_bits = np.argsort(-bits, kind="stable")
+    hot_set = {h: set(by_bits[:h].tolist()) for h in hots}
+    hot_twin = set(select_twin_rows(sample, D, args.hot_twin_cutoff, 64).tolist())
+    hot = {h: collections.Counter() for h in [0] + hots}   # 0 = today
+    dA = np.array([dense.get(int(r), -1) for r in A])
+    dB = np.array([dense.get(int(r), -1) for r in B])
+    for h in hots:
+        hot[h]["queries_answered"] = int(sum(1 for a, b in zip(dA, dB) if a in hot_set[h] and b in hot_set[h]))
 
     def size_class(x):
         for b in (512, 1024, 2048, 2730):
@@ -93,6 +116,7 @@ def main():
         for key in range(16):
             for c0 in range(0, args.batch, args.cq):
                 prev = None
+                hprev = {h: None for h in hot}
                 run = 0
                 npairs = 0
                 for q in range(c0, min(args.batch, c0 + args.cq)):
@@ -107,6 +131,23 @@ def main():
                         probes[size_class(int(n[ib]))] += int(n[ib])
                     ref_bytes += cbytes(tb, n[ib])
                     da, db = dense.get(int(A[q])), dense.get(int(B[q]))
+                    for h, c in hot.items():
+                        if h and da in hot_set[h] and db in hot_set[h]:
+                            continue          # looked up, not counted
+                        a_tw = ta == 1 and n[ia] > args.hot_twin_cutoff and da in hot_twin
+                        b_tw = tb == 1 and n[ib] > args.hot_twin_cutoff and db in hot_twin
+                        c["pairs"] += 1
+                        if tb == 1 and not b_tw:
+                            c["array_probes"] += int(n[ib])
+                        if b_tw:
+                            c["twin_B_pairs"] += 1
+                        elif tb == 2:
+                            c["bitmap_B_pairs"] += 1
+                        c["referenced_bytes"] += 8192 if b_tw else cbytes(tb, n[ib])
+                        if ia != hprev[h]:
+                            c["stagings"] += 1
+                            c["referenced_bytes"] += 8192 if a_tw else cbytes(ta, n[ia])
+                            hprev[h] = ia
                     for t in cuts:
                         a_tw = ta == 1 and n[ia] > t and da in twin_rows[t]
                         b_tw = tb == 1 and n[ib] > t and db in twin_rows[t]
@@ -144,6 +185,15 @@ def main():
     out["twin"] = {str(t): dict({k: round(int(v) * f) for k, v in sorted(tw[t].items())}, rows=len(twin_rows[t]),
                                 extra_bytes_share=round(tw[t]["extra_bytes"] / max(ref_bytes, 1), 4))
                    for t in cuts}
+    today = hot[0]
+    out["hot_pairs"] = {str(h): dict({k: round(int(v) * f) for k, v in sorted(c.items()) if k != "queries_answered"},
+                                     queries_answered_share=round(c["queries_answered"] / args.batch, 4),
+                                     **{k + "_share": round(c[k] / max(today[k], 1), 4)
+                                        for k in ("pairs", "array_probes", "stagings", "referenced_bytes")},
+                                     bitmap_or_twin_B_pairs_share=round(
+                                         (c["twin_B_pairs"] + c["bitmap_B_pairs"]) /
+                                         max(today["twin_B_pairs"] + today["bitmap_B_pairs"], 1), 4))
+                        for h, c in hot.items() if h}
     rl = sorted(runlen.items())
     out["run_length_hist"] = {k: round(v * f) for k, v in rl}
     out["one_off_runs"] = round(runlen[1] * f)
