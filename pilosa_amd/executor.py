@@ -20,6 +20,7 @@ import datetime as dt
 import os
 import re
 import threading
+from fractions import Fraction
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 from pilosa_amd import _roaring
@@ -40,10 +41,24 @@ DEFAULT_FIELD = "general"
 _FANOUT_LOCK = threading.Lock()
 DEFAULT_MIN_THRESHOLD = 1
 MAX_INT = (1 << 63) - 1
+# Percentile(): the device descent (GpuExecutor.bsi_percentile) is the default
+# where it applies; PILOSA_PERCENTILE_DEVICE=0 keeps every call on the generic
+# path (measurements: profiles/percentile/README.md)
+_PERCENTILE_DEVICE_DEFAULT = "1"
 
 
 # a request that is one unfiltered BSI aggregate: Sum|Min|Max(field=<name>)
 _BSI_AGG_RE = re.compile(r"\s*(Sum|Min|Max)\(\s*field\s*=\s*([A-Za-z][A-Za-z0-9_-]*)\s*\)\s*$")
+
+
+def nearest_rank(num: int, den: int, n: int) -> int:
+    """Percentile()'s nearest rank k = max(1, ceil(n * num / den)) in integers
+    (num / den = nth / 100); the one place it is computed."""
+    return max(1, -((-num * n) // den))
+
+
+def _percentile_device() -> bool:
+    return os.environ.get("PILOSA_PERCENTILE_DEVICE", _PERCENTILE_DEVICE_DEFAULT) not in ("0", "")
 
 
 class ExecOptions:
@@ -691,6 +706,8 @@ class Executor:
                 return self._minmax(index, c, shards, opt, "min")
             if n == "Max":
                 return self._minmax(index, c, shards, opt, "max")
+            if n == "Percentile":
+                return self._percentile(index, c, shards, opt)
             if n == "MinRow":
                 return self._minmax_row(index, c, shards, opt, True)
             if n == "MaxRow":
@@ -1297,6 +1314,104 @@ class Executor:
             return self.gpu.bsi_minmax(index, c, ss, which)   # already folded over ss
         r = self.map_reduce(index, shards, c, opt, map_fn, red, local if self.gpu is not None else None) or ValCount()
         return r if r.count else ValCount()
+
+    @staticmethod
+    def percentile_nth(c: Call) -> Fraction:
+        """The ``nth`` argument of Percentile() as an exact rational, from the
+        decimal text of the literal (99.9 is 999/10, never a binary float)."""
+        if "nth" not in c.args:
+            raise PilosaError("Percentile(): nth required")
+        v = c.args["nth"]
+        bad = PilosaError("Percentile(): nth must be a number between 0 and 100")
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise bad
+        try:
+            nth = Fraction(str(v))
+        except (ValueError, ZeroDivisionError):   # nan, inf
+            raise bad
+        if nth < 0 or nth > 100:
+            raise bad
+        return nth
+
+    @staticmethod
+    def percentile_rank(nth: Fraction, n: int) -> int:
+        """Nearest rank: k = max(1, ceil(nth * N / 100)), in integers."""
+        return nearest_rank(nth.numerator, nth.denominator * 100, n)
+
+    def _percentile(self, index: str, c: Call, shards, opt) -> ValCount:
+        """Percentile(field=<int field>, nth=<number>) and Percentile(<one
+        bitmap call>, field=, nth=): exact rank selection over a BSI int field
+        (an extension: Pilosa v1.3 has no such call).
+
+        The considered columns are those with a value in the field
+        (``Row(v != null)``) intersected with the filter child, N of them.
+        The answer is the k-th smallest considered value counting duplicates,
+        k = max(1, ceil(nth * N / 100)) (nearest rank) computed exactly from
+        the decimal text of ``nth``: nth=0 is the minimum, nth=100 the
+        maximum, nth=50 the lower median.  ``ValCount.val`` is that value and
+        ``ValCount.count`` the number of considered columns holding exactly
+        it, summed over ALL shards -- unlike Min / Max, whose count follows
+        the reference and is that of the first shard holding the extreme.
+        N = 0, a missing view, an empty filter or a field that is not a BSI
+        int field give ValCount() (0, 0), as Sum does.
+
+        With a device and only local shards the descent runs on the device
+        (GpuExecutor.bsi_percentile, one launch per bit).  Everywhere else --
+        host, mesh, clusters -- it is a binary search over calls that already
+        exist, at most bit_depth + 4 map/reduce rounds: N = Count(consider),
+        lo / hi = Min / Max, the smallest x in [lo, hi] with
+        Count(Intersect(consider, Row(v <= x))) >= k, and the count of
+        Row(v == x)."""
+        fname = c.args.get("field")
+        if not fname:
+            raise PilosaError("Percentile(): field required")
+        nth = self.percentile_nth(c)
+        if len(c.children) > 1:
+            raise PilosaError("Percentile() only accepts a single bitmap input")
+        f = self.holder.field(index, fname) if isinstance(fname, str) else None
+        if f is None or f.bsi_group(fname) is None:
+            return ValCount()
+        if self._percentile_on_device(index, shards, opt):
+            try:
+                return self.gpu.bsi_percentile(index, c, list(shards))
+            except NotImplementedError:
+                pass   # a filter the device cannot take: the generic path
+            except PilosaError:
+                raise
+            except Exception as err:  # noqa: BLE001 - counted; the generic path answers
+                self._gpu_fault(err)
+        consider = Call("Row", {fname: Condition(NEQ, None)})
+        if c.children:
+            consider = Call("Intersect", {}, [c.children[0].clone(), consider])
+
+        def count(child: Call) -> int:
+            return self._count(index, Call("Count", {}, [child]), shards, opt)
+
+        n = count(consider)
+        if n <= 0:
+            return ValCount()
+        k = self.percentile_rank(nth, n)
+        agg = {"field": fname}
+        kids = [ch.clone() for ch in c.children]
+        lo = self._minmax(index, Call("Min", dict(agg), [ch.clone() for ch in kids]), shards, opt, "min")
+        hi = self._minmax(index, Call("Max", dict(agg), kids), shards, opt, "max")
+        if not lo.count or not hi.count:
+            return ValCount()
+        lo, hi = lo.val, hi.val
+        while lo < hi:   # the smallest x with |consider & (v <= x)| >= k
+            mid = (lo + hi) >> 1
+            if count(Call("Intersect", {}, [consider.clone(), Call("Row", {fname: Condition(LTE, mid)})])) >= k:
+                hi = mid
+            else:
+                lo = mid + 1
+        cnt = count(Call("Intersect", {}, [consider.clone(), Call("Row", {fname: Condition(EQ, lo)})]))
+        return ValCount(lo, cnt) if cnt else ValCount()
+
+    def _percentile_on_device(self, index, shards, opt) -> bool:
+        if self.gpu is None or not _percentile_device() or self._has_remote(index, shards, opt):
+            return False
+        mesh = self.mesh
+        return mesh is None or mesh.world <= 1
 
     def _minmax_row(self, index: str, c: Call, shards, opt, is_min: bool) -> Pair:
         fname = c.args.get("field")

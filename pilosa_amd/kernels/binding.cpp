@@ -253,6 +253,61 @@ void bsi_minmax(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
   check_launch("bsi_minmax");
 }
 
+static void check_kth(const torch::Tensor& views, const torch::Tensor& cand, const torch::Tensor& cnt, int64_t S) {
+  check_dev(views, "views");
+  check_dev(cand, "cand");
+  check_dev(cnt, "cnt");
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 27), "bsi_kth: shard count");
+  TORCH_CHECK(cand.scalar_type() == torch::kInt64 && cand.is_contiguous() && cand.numel() >= S * 16 * 1024,
+              "cand must be int64[S*16*1024]");
+  TORCH_CHECK(cnt.scalar_type() == torch::kInt64 && cnt.is_contiguous() && cnt.numel() >= pk::KTH_CNT,
+              "cnt must be int64[66]");
+}
+
+// Percentile: candidates = exists & filter per (shard, key); cnt[0..1] += N, Nneg (cnt zeroed by the caller)
+void bsi_kth_init(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor bsi_args, torch::Tensor cand,
+                  torch::Tensor cnt) {
+  check_dev(progs, "progs");
+  check_kth(views, cand, cnt, S);
+  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  pk::launch_bsi_kth_init(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
+                          reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S),
+                          bsi_args_from(bsi_args), reinterpret_cast<uint64_t*>(cand.data_ptr<int64_t>()),
+                          reinterpret_cast<unsigned long long*>(cnt.data_ptr<int64_t>()), cur_stream(views));
+  check_launch("bsi_kth_init");
+}
+
+// Percentile: the depth step launches, bit depth-1 .. 0, back to back on the current stream
+void bsi_kth_steps(torch::Tensor views, int64_t S, torch::Tensor bsi_args, torch::Tensor cand, torch::Tensor cnt,
+                   int64_t r, int64_t tot, int64_t largest_first) {
+  check_kth(views, cand, cnt, S);
+  TORCH_CHECK(r >= 0 && tot > 0 && r < tot, "bsi_kth: rank outside the candidate set");
+  const pk::BsiArgs b = bsi_args_from(bsi_args);
+  hipStream_t st = cur_stream(views);
+  for (int i = b.depth - 1; i >= 0; i--)
+    pk::launch_bsi_kth_step(reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+                            reinterpret_cast<uint64_t*>(cand.data_ptr<int64_t>()),
+                            reinterpret_cast<unsigned long long*>(cnt.data_ptr<int64_t>()), i, uint64_t(r),
+                            uint64_t(tot), int(largest_first != 0), st);
+  check_launch("bsi_kth_step");
+}
+
+// Percentile: the host's replay of the chain over cnt1[0..depth) -> (magnitude, count)
+std::tuple<int64_t, int64_t> bsi_kth_replay(torch::Tensor cnt1, int64_t depth, int64_t r, int64_t tot,
+                                            int64_t largest_first) {
+  TORCH_CHECK(!cnt1.is_cuda() && cnt1.scalar_type() == torch::kInt64 && cnt1.is_contiguous() &&
+                  depth >= 0 && depth <= 63 && cnt1.numel() >= depth,
+              "cnt1 must be a cpu int64[depth]");
+  TORCH_CHECK(r >= 0 && tot > 0 && r < tot, "bsi_kth: rank outside the candidate set");
+  const int64_t* c = cnt1.data_ptr<int64_t>();
+  uint64_t ur = uint64_t(r), ut = uint64_t(tot), mag = 0;
+  for (int i = int(depth) - 1; i >= 0; i--) {
+    TORCH_CHECK(c[i] >= 0 && uint64_t(c[i]) <= ut, "bsi_kth: inconsistent bit count");
+    mag |= uint64_t(pk::kth_chain(int(largest_first != 0), uint64_t(c[i]), ur, ut)) << i;
+  }
+  return {int64_t(mag), int64_t(ut)};
+}
+
 void bsi_minmax_fold(torch::Tensor o, int64_t F, int64_t G, int64_t is_min, torch::Tensor out) {
   check_dev(o, "o");
   check_dev(out, "out");
@@ -1074,6 +1129,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsi_range_count", &bsi_range_count, "Count(Row(v <op> x)): fused BSI predicate + count");
   m.def("bsi_minmax", &bsi_minmax, "BSI min/max descents per (shard, key); which: 0 both, 1 Min, 2 Max",
         py::arg("progs"), py::arg("views"), py::arg("S"), py::arg("bsi_args"), py::arg("out"), py::arg("which") = 0);
+  m.def("bsi_kth_init", &bsi_kth_init, "Percentile: candidate tiles (exists & filter) and N, Nneg");
+  m.def("bsi_kth_steps", &bsi_kth_steps, "Percentile: one descent launch per bit, MSB first");
+  m.def("bsi_kth_replay", &bsi_kth_replay, "Percentile: host replay of the bit counts -> (magnitude, count)");
   m.def("leaf_src", &leaf_src, "src containers of plain rows straight from the arena (TopN srcs)");
   m.def("row_counts", &row_counts, "row counts of (shard, dense row) entries (device rank caches)");
   m.def("topn_cache_counts", &topn_cache_counts, "cache-only TopN: [candidate x shard] row counts");

@@ -1348,6 +1348,121 @@ __global__ __launch_bounds__(256, MINW) void bsi_minmax_kernel(const QueryProg* 
   }
 }
 
+// ---------------------------------------------------------------- BSI k-th value
+// Percentile(field=, nth=): the k-th smallest value of exists & filter, exact.
+// An MSB-first descent like Min / Max, but the branch taken at each bit
+// depends on the counts of ALL (shard, key) items, so it is one launch per
+// bit: the launch boundary is the grid-wide barrier.  One wave owns one item;
+// its candidate container lives between launches in a dense buffer
+// cand[S*16][1024].  No launch reads a word it writes: the step for bit i adds
+// to cnt1[i] only and reads cnt1[depth-1 .. i+1], which earlier launches of
+// the same stream finished.
+
+// the block's four waves fold into one atomic per counter (every wave of the
+// launch adding to one word serialises at one L2 channel); slot: a free LDS
+// word per wave.  Every wave of the block must call it.
+__device__ __forceinline__ void kth_block_add(uint64_t* slot, int stride, uint64_t v0, uint64_t v1,
+                                              unsigned long long* out0, unsigned long long* out1) {
+  if (wave_lane() == 0) {
+    slot[0] = v0;
+    slot[1] = v1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t a = 0, b = 0;
+    const uint64_t* base = slot;  // wave 0's slot
+    for (int w = 0; w < WAVES_PER_BLOCK; w++) {
+      a += base[w * stride];
+      b += base[w * stride + 1];
+    }
+    if (a) atomicAdd(out0, (unsigned long long)a);
+    if (b && out1) atomicAdd(out1, (unsigned long long)b);
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void bsi_kth_init_kernel(const QueryProg* __restrict__ progs,
+                                                              const ViewDev* __restrict__ views, int S, BsiArgs bsi,
+                                                              uint64_t* __restrict__ cand,
+                                                              unsigned long long* __restrict__ cnt) {
+  __shared__ WaveScratch scratch[WAVES_PER_BLOCK];
+  const uint32_t blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int wave = threadIdx.x >> 6;
+  const int lane = wave_lane();
+  const int64_t item = int64_t(blk) * WAVES_PER_BLOCK + wave;
+  const bool live = item < int64_t(S) * 16;  // (the block barrier below needs every wave)
+  uint64_t n = 0, nneg = 0;
+  if (live) {
+    const int s = int(item >> 4), j = int(item & 15);
+    const ViewDev& bv = views[bsi.view];
+    WaveScratch& ws = scratch[wave];
+    BsiCtx c{bsi, bv, s, j, bv.shard_base[s], bv.rowptr + int64_t(s) * (bv.D + 1), ws.lb};
+    const QueryProg& qp = progs[0];
+    Tile t;
+    bsi_row(c, bsi.row_exists, t);
+    if (qp.nprog) {
+      uint32_t mask[MAXLEAF];
+      build_slots(qp, views, s, ws, mask);
+      Tile f;
+      if ((candidate_mask(qp, mask) >> j) & 1) eval_tile(qp, views, s, j, ws, f);
+      else tile_zero(f);
+      tile_op<OP_AND>(t, f);
+    }
+    ulong2* dst = reinterpret_cast<ulong2*>(cand + item * 1024);
+#pragma unroll
+    for (int i = 0; i < 8; i++) dst[i * 64 + lane] = t.w[i];
+    n = uint64_t(wave_sum_i64(tile_popc(t)));
+    Tile sign;
+    bsi_row(c, bsi.row_sign, sign);
+    tile_op<OP_AND>(t, sign);
+    nneg = uint64_t(wave_sum_i64(tile_popc(t)));
+  }
+  kth_block_add(scratch[wave].lb, int(sizeof(WaveScratch) / sizeof(uint64_t)), n, nneg, cnt, cnt + 1);
+}
+
+__global__ __launch_bounds__(256) void bsi_kth_step_kernel(const ViewDev* __restrict__ views, int S, BsiArgs bsi,
+                                                           uint64_t* __restrict__ cand, unsigned long long* cnt,
+                                                           int i, uint64_t r, uint64_t tot, int largest_first) {
+  __shared__ uint64_t lbs[WAVES_PER_BLOCK][1024];
+  const uint32_t blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int wave = threadIdx.x >> 6;
+  const int lane = wave_lane();
+  const int64_t item = int64_t(blk) * WAVES_PER_BLOCK + wave;
+  const bool live = item < int64_t(S) * 16;
+  const int depth = bsi.depth;
+  uint64_t c1 = 0;
+  if (live) {
+    const int s = int(item >> 4), j = int(item & 15);
+    const ViewDev& bv = views[bsi.view];
+    // (only planes i and i + 1 are read: each is found as bsi_row finds the
+    // exists row, without plane_index's walk over every plane)
+    BsiCtx c{bsi, bv, s, j, bv.shard_base[s], bv.rowptr + int64_t(s) * (bv.D + 1), lbs[wave]};
+    ulong2* cp = reinterpret_cast<ulong2*>(cand + item * 1024);
+    Tile t, p;
+#pragma unroll
+    for (int w = 0; w < 8; w++) t.w[w] = cp[w * 64 + lane];
+    if (i == depth - 1) {
+      bsi_row(c, bsi.row_sign, p);
+      if (largest_first) tile_op<OP_AND>(t, p);
+      else tile_op<OP_ANDNOT>(t, p);
+    } else {
+      // the decision on bit i + 1: the chain over the counts of the finished launches
+      int bit = 0;
+      for (int b = depth - 1; b > i; b--) bit = kth_chain(largest_first, cnt[2 + b], r, tot);
+      bsi_row(c, bsi.bit_row[i + 1], p);
+      if (bit) tile_op<OP_AND>(t, p);
+      else tile_op<OP_ANDNOT>(t, p);
+    }
+    if (i > 0) {  // (nothing reads the candidates after the last bit's step)
+#pragma unroll
+      for (int w = 0; w < 8; w++) cp[w * 64 + lane] = t.w[w];
+    }
+    bsi_row(c, bsi.bit_row[i], p);
+    tile_op<OP_AND>(t, p);
+    c1 = uint64_t(wave_sum_i64(tile_popc(t)));
+  }
+  kth_block_add(lbs[wave], 1024, c1, 0, cnt + 2 + i, nullptr);
+}
+
 // Fold of the per-key descents into the call's ONE (value, count), on the
 // device (one small D2H instead of the [S, 16, 10] table): per fragment (its
 // G = 16 * sub-shards keys) fragment.min/max's sign rules -- Min: the largest
@@ -1649,6 +1764,22 @@ void launch_bsi_minmax(const QueryProg* progs, const ViewDev* views, int S, BsiA
     hipLaunchKernelGGL((bsi_minmax_kernel<2, 2>), grid, block, 0, st, progs, views, S, bsi, out);
   else
     hipLaunchKernelGGL((bsi_minmax_kernel<0, 2>), grid, block, 0, st, progs, views, S, bsi, out);
+}
+
+void launch_bsi_kth_init(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, uint64_t* cand,
+                         unsigned long long* cnt, hipStream_t st) {
+  const int64_t items = int64_t(S) * 16;
+  if (items == 0) return;
+  hipLaunchKernelGGL(bsi_kth_init_kernel, dim3(grid_for(items)), dim3(64 * WAVES_PER_BLOCK), 0, st, progs, views, S,
+                     bsi, cand, cnt);
+}
+
+void launch_bsi_kth_step(const ViewDev* views, int S, BsiArgs bsi, uint64_t* cand, unsigned long long* cnt, int i,
+                         uint64_t r, uint64_t tot, int largest_first, hipStream_t st) {
+  const int64_t items = int64_t(S) * 16;
+  if (items == 0 || i < 0 || i >= bsi.depth) return;
+  hipLaunchKernelGGL(bsi_kth_step_kernel, dim3(grid_for(items)), dim3(64 * WAVES_PER_BLOCK), 0, st, views, S, bsi,
+                     cand, cnt, i, r, tot, largest_first);
 }
 
 void launch_bsi_minmax_fold(const int64_t* o, int F, int G, int is_min, int64_t* out, int64_t* part,

@@ -96,6 +96,31 @@ void launch_bsi_minmax_fold(const int64_t* o, int F, int G, int is_min, int64_t*
                             hipStream_t st);
 void launch_bsi_minmax(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int64_t* out,
                        hipStream_t st, int which = 0);
+// Percentile(field=, nth=): exact rank selection by an MSB-first descent whose
+// branch at each bit is global (bitmap_kernels.hip bsi_kth_*).  One step of
+// the chain, shared by the step kernel (every wave replays the bits already
+// decided) and the host (the final replay): the current candidate set holds
+// ``tot`` values of which ``c1`` have the bit set, ``r`` is the 0-based rank
+// sought inside it -- counted from the smallest magnitude (largest_first = 0,
+// non-negative answers) or from the largest (1, negative answers).  Returns
+// the bit and narrows (r, tot) to the branch taken.
+__host__ __device__ inline int kth_chain(int largest_first, uint64_t c1, uint64_t& r, uint64_t& tot) {
+  const uint64_t c0 = tot - c1;
+  if (largest_first) {
+    if (r < c1) { tot = c1; return 1; }
+    r -= c1; tot = c0; return 0;
+  }
+  if (r < c0) { tot = c0; return 0; }
+  r -= c0; tot = c1; return 1;
+}
+constexpr int KTH_CNT = 2 + 64;  // cnt[0] = N, cnt[1] = Nneg, cnt[2 + i] = cnt1[i]
+// init: cand[S*16][1024] = exists & filter per (shard, key); cnt[0] += |cand|, cnt[1] += |cand & sign|
+void launch_bsi_kth_init(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, uint64_t* cand,
+                         unsigned long long* cnt, hipStream_t st);
+// step for bit i (depth-1 .. 0): narrow cand by the decision on bit i+1 (the
+// sign restriction at i == depth-1), cnt[2 + i] += |cand & plane i|
+void launch_bsi_kth_step(const ViewDev* views, int S, BsiArgs bsi, uint64_t* cand, unsigned long long* cnt, int i,
+                         uint64_t r, uint64_t tot, int largest_first, hipStream_t st);
 // fmode: 0 no filters, 1 flat-fold filter programs, 2 any program.
 void launch_bsi_sum(const QueryProg* progs, int Q, const ViewDev* views, int S, BsiArgs bsi,
                     unsigned long long* out_sum, unsigned long long* out_cnt, int fmode, hipStream_t st);

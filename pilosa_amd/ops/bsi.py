@@ -155,3 +155,43 @@ def bsi_sum_matrix(engine: GpuEngine, filters: Sequence[Optional[object]], bv: D
     out_s = ((C[:, :depth] - C[:, depth:2 * depth]) * w).sum(dim=1)
     out_c = C[:, 2 * depth]
     return out_s, out_c
+
+
+# ---------------------------------------------------------------- Percentile
+# The chain of the device descent (kernels.h kth_chain, bitmap_kernels.hip
+# bsi_kth_step) in Python: the same rule, line for line, so it can be checked
+# against brute force without a device (tests/test_percentile.py).
+
+def kth_chain(largest_first: bool, c1: int, r: int, tot: int) -> Tuple[int, int, int]:
+    """One bit of the descent.  The candidate set holds ``tot`` values, ``c1``
+    of them with the bit set; ``r`` is the 0-based rank sought in it, counted
+    from the smallest magnitude (or from the largest).  -> (bit, r, tot) of
+    the branch taken."""
+    c0 = tot - c1
+    if largest_first:
+        if r < c1:
+            return 1, r, c1
+        return 0, r - c1, c0
+    if r < c0:
+        return 0, r, c0
+    return 1, r - c0, c1
+
+
+def kth_plan(k: int, n: int, nneg: int) -> Tuple[bool, int, int]:
+    """(largest_first, r, tot) of the descent for the k-th smallest (1-based)
+    of n values, nneg of them negative: a negative answer is the (k - 1)-th
+    largest magnitude of the negatives, a non-negative one the
+    (k - 1 - nneg)-th smallest of the rest."""
+    if k <= nneg:
+        return True, k - 1, nneg
+    return False, k - 1 - nneg, n - nneg
+
+
+def kth_replay(cnt1: Sequence[int], depth: int, largest_first: bool, r: int, tot: int) -> Tuple[int, int]:
+    """Replay the chain over cnt1[depth-1 .. 0] (cnt1[i] = candidates with bit
+    i set when bit i was decided) -> (magnitude, values holding it)."""
+    mag = 0
+    for i in range(depth - 1, -1, -1):
+        bit, r, tot = kth_chain(largest_first, int(cnt1[i]), r, tot)
+        mag |= bit << i
+    return mag, tot

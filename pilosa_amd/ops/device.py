@@ -2045,9 +2045,11 @@ class GpuEngine:
         v, c, found = self.to_host(out).tolist()
         return int(v), int(c), bool(found)
 
-    def _bsi_minmax_dev(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, which: str = ""):
-        torch = self.torch
-        S = bsi_view.S
+    @staticmethod
+    def _bsi_filter_program(filt: Optional[object], bsi_view: "DeviceView"):
+        """(one packed filter program -- the empty one for ``filt`` None --, its
+        views in slot order with the BSI view in slot 0) of a filtered BSI
+        aggregate (Min / Max, Percentile)."""
         view_index: Dict[int, int] = {id(bsi_view): 0}
         views = {id(bsi_view): bsi_view}
         if filt is not None:
@@ -2064,6 +2066,53 @@ class GpuEngine:
         ordered = [None] * len(view_index)
         for vid, slot in view_index.items():
             ordered[slot] = views[vid]
+        return progs, ordered
+
+    def bsi_kth(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, num: int,
+                den: int) -> Optional[Tuple[int, int]]:
+        """The k-th smallest base-relative value of exists & filter, k =
+        max(1, ceil(N * num / den)) (nearest rank; num / den = nth / 100 as an
+        exact fraction): (value, columns holding it), None when no column is
+        considered.  bsi_kth_init stores the candidate tiles and
+        counts N and Nneg (one 16-byte D2H, the rank k is computed exactly
+        from them); then one bsi_kth_step launch per bit, MSB first, back to
+        back; the bit counts come back in one D2H and the chain is replayed
+        on the host (kernels.h kth_chain).
+
+        The candidate buffer is S * 128 KiB of device memory (125 MB at 954
+        shards) allocated per request from torch's caching allocator, outside
+        the arenas' ``hbm_budget`` accounting; concurrent requests hold one
+        each until they return."""
+        torch = self.torch
+        S = bsi_view.S
+        progs, ordered = self._bsi_filter_program(filt, bsi_view)
+        args = self.bsi_args(bsi_view, depth)
+        if not S or args[2] < 0:
+            return None
+        cand = torch.empty(S * 16 * 1024, dtype=torch.int64, device=self.device)
+        cnt = torch.zeros(66, dtype=torch.int64, device=self.device)
+        tp, tv = self.upload_batch(progs, ordered)
+        targs = torch.from_numpy(args)
+        self.ext.bsi_kth_init(tp, tv, S, targs, cand, cnt)
+        n, nneg = (int(x) for x in self.to_host(cnt[:2]).tolist())
+        if n <= 0:
+            return None
+        from pilosa_amd.executor import nearest_rank
+        from .bsi import kth_plan
+        largest, r, tot = kth_plan(nearest_rank(num, den, n), n, nneg)
+        largest = int(largest)
+        if depth > 0:
+            self.ext.bsi_kth_steps(tv, S, targs, cand, cnt, r, tot, largest)
+            cnt1 = self.to_host(cnt[2:2 + depth])
+        else:
+            cnt1 = torch.zeros(0, dtype=torch.int64)
+        mag, count = self.ext.bsi_kth_replay(cnt1.contiguous(), depth, r, tot, largest)
+        return (-int(mag) if largest else int(mag)), int(count)
+
+    def _bsi_minmax_dev(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, which: str = ""):
+        torch = self.torch
+        S = bsi_view.S
+        progs, ordered = self._bsi_filter_program(filt, bsi_view)
         out = torch.zeros(S * 16 * 10, dtype=torch.int64, device=self.device)
         args = self.bsi_args(bsi_view, depth)
         if S and args[2] >= 0:

@@ -8,6 +8,8 @@ device arenas of the involved field-views:
 * ``count``     Count(<bitmap tree>)                 -> expr_count
 * ``bitmap``    Row/Intersect/Union/Difference/Xor/Not/time ranges -> materialize
 * ``bsi_sum``   Sum(<filter>, field=f)                -> bsi_sum kernel
+* ``bsi_percentile`` Percentile(<filter>, field=f, nth=p) -> bsi_kth_init +
+                one bsi_kth_step launch per bit (global MSB-first descent)
 * ``topn``      TopN phase-1/phase-2 with src          -> slot-index LDS
                 histogram + in-kernel heap walk (ops/topn_index.py); while
                 that index is stale: per-shard pair counts + the reference
@@ -163,6 +165,7 @@ class GpuExecutor:
         self._bsi_views: Dict[Tuple, DeviceView] = {}  # predicate results (small LRU)
         self.mu = threading.RLock()
         self.launches = 0
+        self.percentile_device = 0       # Percentile() calls answered by bsi_percentile (the fast path)
         # serving Count text path: host prep (parse..launch) vs result wait
         self.text_batches = 0
         self.text_prep_s = 0.0
@@ -381,7 +384,8 @@ class GpuExecutor:
         return {"arenas": len(views), "arenaBytes": self.hbm_bytes(), "containers": types,
                 "launches": self.launches, "rebuilds": self.rebuilds, "shardUpdates": self.shard_updates,
                 "rowUpdates": self.row_updates, "deviceWrites": self.device_writes,
-                "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget}
+                "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
+                "percentileDevice": self.percentile_device}
 
     def invalidate(self):
         with self.mu:
@@ -581,6 +585,40 @@ class GpuExecutor:
         if not found or n <= 0:
             return ValCount()
         return ValCount(v + b.base, n)
+
+    def bsi_percentile(self, index: str, c: Call, shards: List[int]):
+        """Percentile(<filter>, field=, nth=) over the local shards -> ONE
+        ValCount (value, columns holding it in all shards): the k-th smallest
+        value of exists & filter by an MSB-first descent whose branch at each
+        bit is decided from the counts of all shards (bsi_kth_init, then one
+        bsi_kth_step launch per bit; GpuEngine.bsi_kth)."""
+        from pilosa_amd.executor import Executor, ValCount
+        fname = c.args.get("field")
+        f = self.holder.field(index, fname) if isinstance(fname, str) else None
+        if f is None or f.bsi_group(fname) is None or len(c.children) > 1:
+            raise NotImplementedError
+        nth = Executor.percentile_nth(c)
+        b = f.bsi_group(fname)
+        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
+        if bv is None:
+            self.percentile_device += 1   # no BSI view: answered here, without a launch
+            return ValCount()
+        filt = None
+        if len(c.children) == 1:
+            filt = self.plan(index, c.children[0], shards)
+            if filt is EMPTY:
+                self.percentile_device += 1   # a filter known empty from the schema: no launch either
+                return ValCount()
+        try:
+            r = self.engine.bsi_kth(filt, bv, b.bit_depth, nth.numerator, nth.denominator * 100)
+        except CompileError:
+            raise NotImplementedError
+        self.percentile_device += 1
+        self.launches += 1   # bsi_kth_init
+        if r is None:        # N == 0, read after init: no step ran
+            return ValCount()
+        self.launches += b.bit_depth
+        return ValCount(r[0] + b.base, r[1])
 
     def hbm_bytes(self) -> int:
         with self.mu:
