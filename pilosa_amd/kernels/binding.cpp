@@ -365,24 +365,7 @@ void and2_count(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
 
 pk::ViewDev viewdev_from(const torch::Tensor& vd);
 
-#ifdef PK_KBENCH
-void shadow_build(torch::Tensor view, int64_t S, torch::Tensor rows, torch::Tensor shadow) {
-  check_dev(rows, "rows");
-  check_dev(shadow, "shadow");
-  TORCH_CHECK(rows.scalar_type() == torch::kInt32, "rows must be int32[R]");
-  const int64_t R = rows.numel();
-  TORCH_CHECK(shadow.scalar_type() == torch::kInt64 && shadow.is_contiguous() && shadow.numel() == R * S * 16 * 1024,
-              "shadow must be int64[R*S*16*1024]");
-  pk::ViewDev v = viewdev_from(view);
-  TORCH_CHECK(R >= 0 && R < (int64_t(1) << 20) && S > 0, "shadow_build sizes");
-  pk::launch_shadow_build(v, int(S), rows.data_ptr<int32_t>(), int(R), reinterpret_cast<uint64_t*>(shadow.data_ptr<int64_t>()),
-                          cur_stream(shadow));
-  check_launch("shadow_build");
-}
-#endif  // PK_KBENCH
-
-// Bitmap twins of dense array rows (DeviceView.ensure_twin): the shadow build
-// kernel over another row list.
+// Bitmap twins of dense array rows (DeviceView.ensure_twin).
 void twin_build(torch::Tensor view, int64_t S, torch::Tensor rows, torch::Tensor twin) {
   check_dev(rows, "rows");
   check_dev(twin, "twin");
@@ -392,7 +375,7 @@ void twin_build(torch::Tensor view, int64_t S, torch::Tensor rows, torch::Tensor
   TORCH_CHECK(twin.scalar_type() == torch::kInt64 && twin.numel() == R * S * 16 * 1024,
               "twin must be int64[R*S*16*1024]");
   pk::ViewDev v = viewdev_from(view);
-  pk::launch_shadow_build(v, int(S), rows.data_ptr<int32_t>(), int(R), reinterpret_cast<uint64_t*>(twin.data_ptr<int64_t>()),
+  pk::launch_twin_build(v, int(S), rows.data_ptr<int32_t>(), int(R), reinterpret_cast<uint64_t*>(twin.data_ptr<int64_t>()),
                           cur_stream(twin));
   check_launch("twin_build");
 }
@@ -1103,12 +1086,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "gfx950 HIP kernels for the bitmap index";
   m.attr("QUERYPROG_BYTES") = int(sizeof(pk::QueryProg));
   m.attr("VIEWDEV_BYTES") = int(sizeof(pk::ViewDev));
-  // pair-kernel variant ids of the bitmap twins / un-staging built into this module
-#ifdef PK_KBENCH
-  m.attr("PAIR_VARIANTS") = std::vector<int>{61, 62, 63, 64, 65};
-#else
+  // pair-kernel variant ids of the bitmap twins built into this module
   m.attr("PAIR_VARIANTS") = std::vector<int>{63};
-#endif
   m.attr("MAXLEAF") = pk::MAXLEAF;
   m.attr("MAXPROG") = pk::MAXPROG;
   m.def("expr_count", &expr_count, "batched boolean-expression count over all local shards",
@@ -1116,7 +1095,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("per_shard") = py::none());
   m.def("expr_materialize", &expr_materialize, "write result containers for a batch of expressions");
 #ifdef PK_KBENCH
-  m.def("shadow_build", &shadow_build, "dense bitmap shadows of hot rows for the pair kernels");
   m.attr("KBENCH") = true;
 #else
   m.attr("KBENCH") = false;

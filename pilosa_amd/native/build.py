@@ -170,8 +170,7 @@ def hip_sources():
 def build_hip(force: bool = False, verbose: bool = False, kbench: bool = False) -> str:
     """Compile the HIP kernels + torch binding for gfx950 with hipcc.
     ``kbench``: the A/B module ``_hipkernels_kbench`` (-DPK_KBENCH) that also
-    holds the measured-and-rejected kernel variants and the cost-isolation
-    skeletons (scripts/kbench.py, scripts/topn_kbench.py); the shipped
+    holds the TopN cost-isolation bits (scripts/topn_kbench.py); the shipped
     ``_hipkernels`` has none of them."""
     import torch
     from torch.utils import cpp_extension

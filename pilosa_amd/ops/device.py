@@ -49,7 +49,7 @@ _OPS = {"and": OP_AND, "or": OP_OR, "xor": OP_XOR, "andnot": OP_ANDNOT}
 QPROG_DTYPE = np.dtype([("nleaf", "<i4"), ("nprog", "<i4"), ("leaf_view", "<i4", (MAXLEAF,)),
                         ("leaf_row", "<i8", (MAXLEAF,)), ("prog", "u1", (MAXPROG,)), ("pad", "<i8", (3,))])
 VIEWDEV_DTYPE = np.dtype([("rowptr", "<u8"), ("shard_base", "<u8"), ("meta", "<u8"), ("payload", "<u8"),
-                          ("D", "<i8"), ("keymask", "<u8"), ("shadow", "<u8"), ("shadow_slot", "<u8"),
+                          ("D", "<i8"), ("keymask", "<u8"), ("reserved0", "<u8"), ("reserved1", "<u8"),   # unused, zero
                           ("twin", "<u8"), ("twin_slot", "<u8"), ("twin_cutoff", "<i8"),
                           ("hot_counts", "<u8"), ("hot_slot", "<u8"), ("hot_valid", "<u8"), ("hot_h", "<i8")])
 assert QPROG_DTYPE.itemsize == 256 and VIEWDEV_DTYPE.itemsize == 120
@@ -71,8 +71,8 @@ def kernels():
 
                 import torch  # noqa: F401  (loads libtorch for the extension)
                 # PILOSA_HIPKERNELS=_hipkernels_kbench: the A/B build with the
-                # rejected variants (scripts/kbench.py); the product loads the
-                # shipped module
+                # TopN cost-isolation bits (scripts/topn_kbench.py); the
+                # product loads the shipped module
                 ext = importlib.import_module("pilosa_amd." + os.environ.get("PILOSA_HIPKERNELS", "_hipkernels"))
                 assert ext.QUERYPROG_BYTES == QPROG_DTYPE.itemsize
                 assert ext.VIEWDEV_BYTES == VIEWDEV_DTYPE.itemsize
@@ -861,8 +861,9 @@ class DeviceView:
     def nbytes(self) -> int:
         n = sum(t.numel() * t.element_size() for t in (self.t_rowptr, self.t_shard_base, self.t_meta,
                                                        self.t_payload))
-        for sh in (getattr(self, "_shadow", None), getattr(self, "_twin", None)):
-            n += sh[1].numel() * 8 + sh[2].numel() * 4 if sh is not None else 0
+        tw = getattr(self, "_twin", None)
+        if tw is not None:
+            n += tw[1].numel() * 8 + tw[2].numel() * 4
         hp = getattr(self, "_hot", None)
         if hp is not None:
             n += hp.counts.numel() * 4 + hp.slot.numel() * 4 + hp.valid.numel()
@@ -895,10 +896,6 @@ class DeviceView:
         km = getattr(self, "_keymask", None)
         if km is not None and km[0] == self.generation:
             rec["keymask"] = km[1].data_ptr()
-        sh = getattr(self, "_shadow", None)
-        if sh is not None and sh[0] == self.generation:
-            rec["shadow"] = sh[1].data_ptr()
-            rec["shadow_slot"] = sh[2].data_ptr()
         tw = getattr(self, "_twin", None)
         if tw is not None and tw[0] == self.generation:
             rec["twin"] = tw[1].data_ptr()
@@ -912,22 +909,13 @@ class DeviceView:
             rec["hot_h"] = hp.h
         return rec
 
-    def shadow_fresh(self) -> bool:
-        sh = getattr(self, "_shadow", None)
-        return sh is not None and sh[0] == self.generation
-
-    # dense bitmap shadows of the hottest rows (pair_kernels.hip SHD): up to
-    # SHADOW_ROWS rows, within SHADOW_MAX_BYTES and a quarter of free HBM
-    SHADOW_ROWS = int(os.environ.get("PILOSA_SHADOW_ROWS", "256"))
-    SHADOW_MAX_BYTES = int(os.environ.get("PILOSA_SHADOW_MAX_GB", "40")) << 30
-    SHADOW_MIN_INTERVAL_S = 30.0
-    SHADOW_SAMPLE_SHARDS = 8
+    HOT_SAMPLE_SHARDS = 8
 
     def _hot_dense_rows(self, R: int) -> np.ndarray:
         """The R dense rows with the most bits over a sample of shards
         (a hot row of a Zipf-like field is hot in every shard)."""
         D1 = self.D + 1
-        picks = sorted(set(np.linspace(0, self.S - 1, min(self.S, self.SHADOW_SAMPLE_SHARDS)).astype(int).tolist()))
+        picks = sorted(set(np.linspace(0, self.S - 1, min(self.S, self.HOT_SAMPLE_SHARDS)).astype(int).tolist()))
         tot = np.zeros(self.D, np.int64)
         sb = self._sb_host
         for si in picks:
@@ -945,50 +933,6 @@ class DeviceView:
         top = np.argpartition(-tot, R - 1)[:R]
         return np.sort(top).astype(np.int32)
 
-    def ensure_shadow(self) -> bool:
-        """Build (or refresh, at most every SHADOW_MIN_INTERVAL_S after
-        writes) the dense bitmap shadows of this view's hottest rows: each
-        row's container of every (shard, key) as a 1024-word bitmap in HBM,
-        so the pair kernels stage it with one coalesced copy or read it in
-        place.  A stale shadow is simply not passed.  Returns whether it is
-        fresh."""
-        import time
-
-        import torch
-
-        if self.SHADOW_ROWS <= 0 or self.device.type != "cuda" or not self.S or not self.D or \
-                not hasattr(kernels(), "shadow_build"):
-            return False
-        sh = getattr(self, "_shadow", None)
-        if sh is not None and sh[0] == self.generation:
-            return True
-        now = time.monotonic()
-        if sh is not None and now - sh[3] < self.SHADOW_MIN_INTERVAL_S:
-            return False
-        if sh is None and getattr(self, "_shadow_declined", None) == self.generation:
-            return False
-        per_row = self.S * 16 * 8192
-        free, _ = torch.cuda.mem_get_info(self.device)
-        R = min(self.SHADOW_ROWS, self.D, int(min(free // 4, self.SHADOW_MAX_BYTES) // per_row))
-        rows = self._hot_dense_rows(R) if R >= 8 else np.zeros(0, np.int32)
-        if len(rows) < 8:
-            self._shadow_declined = self.generation
-            return False
-        R = len(rows)
-        buf = sh[1] if sh is not None and sh[1].numel() == R * self.S * 16 * 1024 else None
-        if buf is None:
-            self._shadow = None
-            buf = torch.empty(R * self.S * 16 * 1024, dtype=torch.int64, device=self.device)
-        slot = torch.full((self.D,), -1, dtype=torch.int32)
-        slot[torch.from_numpy(rows.astype(np.int64))] = torch.arange(R, dtype=torch.int32)
-        slot = slot.to(self.device)
-        self.ensure_keymask()
-        kernels().shadow_build(self.viewdev_tensor(), self.S, torch.from_numpy(rows).to(self.device), buf)
-        # readers on any stream see a complete shadow
-        torch.cuda.current_stream(self.device).synchronize()
-        self._shadow = (self.generation, buf, slot, now, rows)
-        return True
-
     # bitmap twins of dense ARRAY rows (pair_kernels.hip TWN): up to TWIN_ROWS
     # rows, within a quarter of free HBM; a container is read through its twin
     # only while it is an array of more than TWIN_CUTOFF values
@@ -1004,7 +948,7 @@ class DeviceView:
         """(rowptr int64[D+1], meta int64[n]) of the sampled shards (the
         sample of :meth:`_hot_dense_rows`)."""
         D1 = self.D + 1
-        picks = sorted(set(np.linspace(0, self.S - 1, min(self.S, self.SHADOW_SAMPLE_SHARDS)).astype(int).tolist()))
+        picks = sorted(set(np.linspace(0, self.S - 1, min(self.S, self.HOT_SAMPLE_SHARDS)).astype(int).tolist()))
         out = []
         for si in picks:
             rp = self.t_rowptr[si * D1:(si + 1) * D1].cpu().numpy().astype(np.int64)
@@ -1016,7 +960,7 @@ class DeviceView:
         """Build (or refresh, at most every TWIN_MIN_INTERVAL_S after writes)
         the bitmap twins of this view's dense array rows
         (:func:`select_twin_rows`): every (shard, key) container of such a row
-        as a 1024-word bitmap in HBM, laid out like the shadows.  The pair
+        as a 1024-word bitmap in HBM (ViewDev.twin).  The pair
         kernel reads a twin instead of an array container of more than
         TWIN_CUTOFF values, on either side of a pair.  The twin is tied to
         the view generation and a stale one is not passed, so answers never
@@ -1378,21 +1322,11 @@ class GpuEngine:
         self.use_and2 = os.environ.get("PILOSA_AND2", "1") != "0"
         self.and2_cq = int(os.environ.get("PILOSA_AND2_CQ", "0"))  # 0 = by batch size
         self.and2_variant = int(os.environ.get("PILOSA_AND2_VARIANT", "6"))
-        # dense bitmap shadows of hot rows for the pair kernels (DeviceView.ensure_shadow)
-        # (off by default: measured slower -- headline 16.66 vs 16.45 ms, serving
-        # 61.5k vs 69.3k req/s, profiles/r05_serve/ -- the staged LDS probes beat
-        # reading a 8 KiB shadow in place, and the hot A rows are mostly bitmaps)
-        # dense shadows of hot rows (variants 41 / 42): measured slower, built
-        # into the kbench module only (profiles/r05_shadow/)
-        self.use_shadow = os.environ.get("PILOSA_SHADOW", "0") != "0" and hasattr(kernels(), "shadow_build")
         # the 64-queries-per-wave pair kernel reads dense array rows through
         # their bitmap twins (DeviceView.ensure_twin, pair_kernels.hip TWN:
-        # 15.05 vs 16.30 ms per 4096-query headline batch).  Un-staging of
-        # small arrays (UNS) measured slower (16.73 ms) and is built into the
-        # kbench module only (profiles/pairs_twin/)
+        # 15.05 vs 16.30 ms per 4096-query headline batch, profiles/pairs_twin/)
         built = set(getattr(kernels(), "PAIR_VARIANTS", ()))
         self.use_twin = os.environ.get("PILOSA_TWIN", "1") != "0" and 63 in built
-        self.use_unstage = os.environ.get("PILOSA_UNSTAGE", "0") != "0" and {64, 65} <= built
         # Count(Intersect) of two hot rows of a view is looked up in the view's
         # per-shard hot-pair table by pair_build (DeviceView.ensure_hot); the
         # launcher hands it to the shipped kernels only (v6, 39, 63)
@@ -1403,17 +1337,14 @@ class GpuEngine:
         self.union_variant = int(os.environ.get("PILOSA_UNION_VARIANT", "2"))
 
     def _and2_aux(self, views: List["DeviceView"], n: int) -> int:
-        """Side structures of a batch with ``n`` Count(Intersect) queries: 1 =
-        a view carries dense shadows, 2 = a view carries fresh bitmap twins, 0
-        = neither.  Twins are ensured only for batches that run the
-        64-queries-per-wave pair kernel."""
+        """Side structures of a batch with ``n`` Count(Intersect) queries: 2 =
+        a view carries fresh bitmap twins, 0 = none.  Twins are ensured only
+        for batches that run the 64-queries-per-wave pair kernel."""
         if self.use_hot and self.and2_variant in (6, 39, 63):   # any batch size
             for v in views:
                 v.ensure_hot()
-        if self.use_shadow and any([v.ensure_shadow() for v in views]):
-            return 1
         wave64 = self.and2_cq == 64 or (self.and2_cq <= 0 and n > 2048)
-        if self.use_twin and wave64 and self.and2_variant in (6, 61, 62, 63, 65) and \
+        if self.use_twin and wave64 and self.and2_variant in (6, 63) and \
                 any([v.ensure_twin() for v in views]):
             return 2
         return 0
@@ -1621,19 +1552,15 @@ class GpuEngine:
 
     def _and2_partial(self, tp, tv, S: int, n: int, shd: int = 0):
         """Per-(shard, key, query) Count(Intersect) partials -> int32[S, 16, n].
-        ``shd`` (:meth:`_and2_aux`) 1: a view of the batch carries dense
-        shadows (variant 41; the launcher takes 42 for serving-size batches);
-        2: a view carries fresh bitmap twins (variant 63, with un-staging 65;
-        the launcher runs them at 64 queries per wave only)."""
+        ``shd`` (:meth:`_and2_aux`) 2: a view of the batch carries fresh
+        bitmap twins (variant 63; the launcher runs it at 64 queries per wave
+        only)."""
         torch = self.torch
         pairs = torch.empty(S * 16 * n * 2, dtype=torch.int32, device=self.device)
         partial = torch.empty(S * 16 * n, dtype=torch.int32, device=self.device)
         variant = self.and2_variant
-        if variant == 6 and shd == 1:
-            variant = 41
-        elif variant == 6:
-            variant = {(True, True): 65, (True, False): 63, (False, True): 64}.get(
-                (shd == 2 and self.use_twin, self.use_unstage), 6)
+        if variant == 6 and shd == 2 and self.use_twin:
+            variant = 63
         self.ext.and2_count(tp, tv, S, pairs, partial, self.and2_cq, variant)
         return partial.view(S, 16, n)
 

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Compare the gfx950 code of one .hip file between two revisions, kernel by kernel.
+
+  python scripts/isa_compare.py REV_A REV_B pilosa_amd/kernels/pair_kernels.hip
+
+REV is anything `git archive` takes, or `.` for the working tree.  Each side's
+kernel directory (so its own kernels.h) goes to a temp directory and is
+cross-compiled to assembly; no GPU is needed.  Per kernel the report says
+whether the normalised text (comments stripped, .LBB labels renumbered) is
+identical, and gives VGPRs / SGPRs / LDS / scratch before -> after, the
+instruction count and the opcode-count delta.  Kernels are matched by their
+demangled name; where a template's parameter list differs between the
+revisions, TEMPLATE_KEYS names the parameters that identify an instantiation.
+"""
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+CXXFILT = os.environ.get("CXXFILT", "c++filt")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S"]
+# template name -> {number of template arguments: positions of the identifying ones}
+TEMPLATE_KEYS = {"and2_pairs_v6_kernel": {11: (0, 6, 9), 3: (0, 1, 2)}}   # (CQ, BST, TWN)
+RENAMED = {"shadow_build_kernel": "twin_build_kernel"}
+STATS = (("vgpr", "NumVgprs"), ("sgpr", "TotalNumSgprs"), ("lds", "LDSByteSize"), ("scratch", "ScratchSize"))
+
+
+def assembly(rev, path, tmp):
+    src = os.path.dirname(path) or "."
+    if rev != ".":
+        src = os.path.join(tmp, "src")
+        os.makedirs(src)
+        tar = subprocess.run(["git", "archive", rev, "--", os.path.dirname(path)], check=True, capture_output=True)
+        subprocess.run(["tar", "-x", "--strip-components", str(path.count("/")), "-C", src], input=tar.stdout, check=True)
+    out = os.path.join(tmp, "out.s")
+    subprocess.run([HIPCC, *FLAGS, os.path.join(src, os.path.basename(path)), "-o", out], check=True)
+    return open(out).read()
+
+
+def key_of(mangled):
+    name = subprocess.run([CXXFILT, mangled], check=True, capture_output=True, text=True).stdout.strip()
+    m = re.match(r"(?:void )?(?:[\w:]|\(anonymous namespace\))*?(\w+)(?:<(.*?)>)?\(", name)
+    base, args = m.group(1), [a.strip() for a in (m.group(2) or "").split(",") if a.strip()]
+    pos = TEMPLATE_KEYS.get(base, {}).get(len(args))
+    norm = {"false": "0", "true": "1"}
+    args = [norm.get(args[p], args[p]) for p in pos] if pos else args
+    return RENAMED.get(base, base) + ("<" + ", ".join(args) + ">" if args else "")
+
+
+def kernels(asm):
+    """{key: (normalised instruction lines, {stat: value})} of every kernel in the assembly"""
+    out = {}
+    for m in re.finditer(r"^(\w+):\s*; @\1\n(.*?)^\.Lfunc_end\d+:\n(.*?)^; Occupancy", asm, re.M | re.S):
+        if ".amdhsa_kernel " + m.group(1) not in asm:
+            continue
+        labels, lines = {}, []
+        for ln in m.group(2).splitlines():
+            ln = re.sub(r"\.LBB\d+_\d+", lambda l: labels.setdefault(l.group(0), ".L%d" % len(labels)),
+                        ln.split(";")[0].strip())
+            if ln and not ln.startswith("."):
+                lines.append(ln)
+            elif ln.endswith(":"):
+                lines.append(ln)
+        stats = {k: int(re.search(r"; %s: (\d+)" % tag, m.group(3)).group(1)) for k, tag in STATS}
+        out[key_of(m.group(1))] = (lines, stats)
+    return out
+
+
+def opcodes(lines):
+    return collections.Counter(ln.split()[0] for ln in lines if not ln.endswith(":"))
+
+
+def main():
+    rev_a, rev_b, path = sys.argv[1:4]
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+        a, b = kernels(assembly(rev_a, path, ta)), kernels(assembly(rev_b, path, tb))
+    print("%s: %s -> %s (%s)" % (path, rev_a, rev_b, " ".join(FLAGS)))
+    same = 0
+    for key in sorted(set(a) | set(b)):
+        if key not in a or key not in b:
+            print("%-40s only in %s" % (key, rev_a if key in a else rev_b))
+            continue
+        (la, sa), (lb, sb) = a[key], b[key]
+        same += la == lb
+        oa, ob = opcodes(la), opcodes(lb)
+        na, nb = sum(oa.values()), sum(ob.values())
+        print("%-40s %s  %s  insts %d -> %d" % (key, "identical" if la == lb else "DIFFERENT", "  ".join(
+            "%s %d -> %d" % (k, sa[k], sb[k]) for k, _ in STATS), na, nb))
+        delta = {op: ob[op] - oa[op] for op in sorted(set(oa) | set(ob)) if ob[op] != oa[op]}
+        if delta:
+            print("    opcode delta: " + ", ".join("%s %+d" % kv for kv in delta.items()))
+    print("%d of %d kernels identical" % (same, len(set(a) | set(b))))
+
+
+if __name__ == "__main__":
+    main()

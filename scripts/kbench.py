@@ -3,14 +3,14 @@
 (launch_count) of a Count(Intersect) batch for several engine settings with
 HIP events.  Usage: python scripts/kbench.py [--batch 1024] [--reps 5] [--shards N]
 
-Pair-kernel variant ids of the bitmap twins / un-staging (64 queries per
-wave): 61 twinned A only, 62 twinned B only, 63 both, 64 un-staging only, 65
-both twins + un-staging; --twin-cutoff lists the cutoffs T each twin variant
-is timed at (the twin is rebuilt per T).  6 = the plain v6 kernel; a variant
-may be listed several times to alternate it with others.  --hot-rows times
-the shipped kernels with the hot-pair table of H rows (DeviceView.ensure_hot)
-next to H = 0 on the same arena, and prints how many entries it answers.
-PILOSA_HIPKERNELS=_hipkernels runs the shipped module (variants 6 and 63)."""
+Pair-kernel variants (--variants): 6 = the plain v6 kernel (39, batched
+staging, for batches of up to 128 queries when the chunk size is 0), 63 = the
+bitmap twins (64 queries per wave); --twin-cutoff lists the cutoffs T variant
+63 is timed at (the twin is rebuilt per T).  A variant may be listed several
+times to alternate it with others.  --hot-rows times the kernels with the
+hot-pair table of H rows (DeviceView.ensure_hot) next to H = 0 on the same
+arena, and prints how many entries it answers.  The pair kernels are the same
+in both modules; PILOSA_HIPKERNELS=_hipkernels runs the shipped one."""
 import argparse
 import json
 import math
@@ -21,8 +21,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the A/B module: the shipped variants plus every rejected one and the
-# cost-isolation skeletons (python -m pilosa_amd.native.build --kbench)
+# the A/B module: the shipped kernels plus the TopN cost-isolation bits
+# (python -m pilosa_amd.native.build --kbench)
 os.environ.setdefault("PILOSA_HIPKERNELS", "_hipkernels_kbench")
 sys.path.insert(0, ROOT)
 
@@ -36,8 +36,8 @@ def main():
     ap.add_argument("--shards", type=int, default=0, help="0 = full 954")
     ap.add_argument("--cq", default="0,32,64", help="pair-kernel chunk sizes (queries per wave)")
     ap.add_argument("--no-tile", action="store_true", help="skip the generic tile kernel")
-    ap.add_argument("--variants", default="", help="extra kernel variants at --cq's first size, e.g. 4,5 (38@8: at 8 queries per wave)")
-    ap.add_argument("--twin-cutoff", default="", help="twin cutoffs T for variants 61/62/63/65, e.g. 3072,2730,2048 "
+    ap.add_argument("--variants", default="", help="pair-kernel variants at --cq's first size, e.g. 6,63 (39@8: at 8 queries per wave)")
+    ap.add_argument("--twin-cutoff", default="", help="twin cutoffs T for variant 63, e.g. 3072,2730,2048 "
                     "(default: DeviceView.TWIN_CUTOFF)")
     ap.add_argument("--hot-rows", default="", help="hot-pair table sizes H each --variants setting of the shipped "
                     "kernels (6, 39, 63) is timed at, e.g. 0,128,256,512 (0 = no table; default: no table)")
@@ -65,9 +65,9 @@ def main():
     for v in args.variants.split(","):
         if not v:
             continue
-        vv, _, cq = v.partition("@")   # "38@8": variant 38 at 8 queries per wave
+        vv, _, cq = v.partition("@")   # "39@8": variant 39 at 8 queries per wave
         cq = int(cq) if cq else cq0
-        cuts = [int(t) for t in args.twin_cutoff.split(",") if t] if int(vv) in (61, 62, 63, 65) else []
+        cuts = [int(t) for t in args.twin_cutoff.split(",") if t] if int(vv) == 63 else []
         hots = [int(h) for h in args.hot_rows.split(",") if h] if int(vv) in (6, 39, 63) else []
         for t in cuts or [None]:
             for hr in hots or [0]:
@@ -81,8 +81,7 @@ def main():
         hot = cfg.pop("hot_rows", 0)
         for k, v in cfg.items():
             setattr(eng, k, v)
-        eng.use_unstage = eng.use_twin = False      # variants are explicit here: 6 is the plain kernel
-        eng.use_twin = cfg.get("and2_variant") in (61, 62, 63, 65)
+        eng.use_twin = cfg.get("and2_variant") == 63   # variants are explicit here: 6 is the plain kernel
         if cut is not None and (view.TWIN_CUTOFF != cut or not view.twin_fresh()):
             view._twin = None        # rebuilt at this cutoff by prepare_progs
             view.TWIN_CUTOFF = cut

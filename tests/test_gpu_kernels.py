@@ -126,8 +126,7 @@ def test_and2_pair_kernels_match_tile_kernel(setup):
         exprs.append(Op("and", (Leaf(va, min(a, 5) if va is view2 else a), Leaf(view, b))))
         ra = min(a, 5) if va is view2 else a
         want.append(sum(_row(x, ra).intersection_count(_row(f, b)) for x, f in zip(fa, frags)))
-    # the shipped variants (v6, the serving variant 39); the rejected ones
-    # live in the kbench module only (native/build.py --kbench)
+    # the shipped variants (v6, the serving variant 39)
     for var in (6, 39):
         for cq in (0, 16, 32, 64):
             e2 = GpuEngine(view.device)
@@ -381,48 +380,3 @@ def test_partial_sum_scatter_matches_torch(U, n):
     want2 = want.clone()
     want2[ti[0]] = 0
     assert torch.equal(out2.cpu(), want2)
-
-
-def test_dense_shadows_match_arena_containers():
-    """shadow_build_kernel: every shadowed (row, shard, key) is the row's
-    container of that key as a bitmap (zeros where the row has none); rows are
-    the hottest by bit count; a write leaves the shadow stale (not passed).
-    Dense shadows measured slower and ship in the kbench module only
-    (PILOSA_HIPKERNELS=_hipkernels_kbench runs this test)."""
-    import torch
-
-    from pilosa_amd.ops.device import kernels
-    if not hasattr(kernels(), "shadow_build"):
-        pytest.skip("dense shadows are built into the kbench module only")
-
-    from pilosa_amd.ops.device import DeviceView
-    rng = np.random.default_rng(5)
-    frags = []
-    for s in range(3):
-        rows = rng.zipf(1.5, 60000) % 40
-        cols = rng.integers(0, 1 << 20, 60000)
-        frags.append(R.Bitmap((rows.astype(np.uint64) << np.uint64(20)) + cols.astype(np.uint64)))
-        frags[-1].optimize()
-    dev = torch.device("cuda:0")
-    view = DeviceView.from_bitmaps(frags, dev)
-    assert view.ensure_shadow()
-    gen, buf, slot, _, rows = view._shadow
-    sh = buf.view(len(rows), view.S, 16, 1024).cpu().numpy()
-    counts = [sum(int(f.count_range(int(d_row) << 20, (int(d_row) + 1) << 20)) for f in frags) for d_row in view.rows]
-    assert set(rows.tolist()) <= set(range(view.D)) and len(rows) >= 8
-    # every shard sampled here (S <= SHADOW_SAMPLE_SHARDS): exactly the hottest rows (up to ties)
-    assert sum(counts[d] for d in rows.tolist()) == sum(sorted(counts, reverse=True)[:len(rows)])
-    for r, d in enumerate(rows.tolist()):
-        rid = int(view.rows[d])
-        for s in range(view.S):
-            for j in range(16):
-                lo = (rid << 20) + (j << 16)
-                want = np.zeros(65536, bool)
-                got_cols = frags[s].slice_range(lo, lo + 65536) if hasattr(frags[s], "slice_range") else \
-                    np.asarray([c for c in frags[s].slice() if lo <= c < lo + 65536], np.uint64)
-                want[(np.asarray(got_cols, np.int64) - lo)] = True
-                bits = np.unpackbits(sh[r, s, j].view(np.uint8), bitorder="little").astype(bool)
-                assert np.array_equal(bits, want), (r, s, j)
-    assert slot.cpu().numpy()[rows].tolist() == list(range(len(rows)))
-    view.generation += 1                       # a write: the shadow is not passed until rebuilt
-    assert not view.shadow_fresh() and int(view.viewdev()["shadow"]) == 0

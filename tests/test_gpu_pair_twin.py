@@ -1,6 +1,6 @@
 """Pair kernel (pair_kernels.hip), 64 queries per wave: bitmap twins of dense
-array rows (TWN) and un-staging of small arrays (UNS).  Every count is
-compared exactly with the host roaring oracle, and the flagged kernels'
+array rows (TWN), and the LDS bitmap's clear between stagings.  Every count
+is compared exactly with the host roaring oracle, and the flagged kernels'
 partial buffers with the plain v6 kernel's."""
 import numpy as np
 import pytest
@@ -157,7 +157,7 @@ def test_twin_counts_match_host(nkeys, cpr):
     np.testing.assert_array_equal(eng.to_host(eng.launch_count(handle)).numpy(), want)
     base = _partials(eng, handle, 6)
     assert (base != -7).all()
-    for variant in eng.ext.PAIR_VARIANTS:   # 63 ships; the kbench module holds A only / B only / un-staging too
+    for variant in eng.ext.PAIR_VARIANTS:   # 63 ships
         np.testing.assert_array_equal(_partials(eng, handle, variant), base, err_msg=f"variant {variant}")
     # without twins the flagged kernels take the array paths
     plain = GpuEngine(dev)
@@ -215,9 +215,9 @@ def test_twin_only_for_the_64_query_wave_kernel():
     assert getattr(view, "_twin", None) is None
 
 
-# ---------------------------------------------------------------- un-staging
+# ---------------------------------------------------------------- restaging
 
-def _unstage_case(rng):
+def _restage_case(rng):
     """One shard, key 0.  A rows in kernel order (ascending row id): small,
     small, large array, bitmap, small, small, a one-off array & bitmap pair
     (stages B), small, small.  Every B holds all the values the bitmap staged
@@ -243,12 +243,12 @@ def _unstage_case(rng):
     return R.Bitmap(pos), a_n, prs
 
 
-def test_unstage_leaves_no_stale_bits():
+def test_restaging_leaves_no_stale_bits():
     import torch
     from pilosa_amd.ops.device import DeviceView, GpuEngine, Leaf, Op
 
     rng = np.random.default_rng(24)
-    frag, a_n, prs = _unstage_case(rng)
+    frag, a_n, prs = _restage_case(rng)
     info = {(k >> 4, k & 15): t for k, t, _ in frag.container_info()}
     assert info[(3, 0)] == "bitmap" and info[(30, 0)] == "bitmap" and info[(2, 0)] == "array"
     dev = torch.device("cuda:0")
@@ -258,10 +258,8 @@ def test_unstage_leaves_no_stale_bits():
     assert (want > 0).all()
     eng = GpuEngine(dev)
     eng.and2_cq = 64
-    # un-staging measured slower and is built into the kbench module only;
-    # the shipped kernel walks the same A sequence with a clear per staging
-    uns = 64 in eng.ext.PAIR_VARIANTS
-    eng.and2_variant = 64 if uns else 6
+    # the plain kernel walks the A sequence with a clear per staging
+    eng.and2_variant = 6
     eng.use_twin = False
     handle = eng.prepare_count(exprs)
     ra, _ = _sorted_rows(handle)
