@@ -151,22 +151,35 @@ class FieldRow:
 
 
 class GroupCount:
-    __slots__ = ("group", "count")
+    __slots__ = ("group", "count", "sum", "sum_count")
 
-    def __init__(self, group: List[FieldRow], count: int):
+    def __init__(self, group: List[FieldRow], count: int, sum: Optional[int] = None,
+                 sum_count: Optional[int] = None):
+        # sum / sum_count: GroupBy(..., aggregate=Sum(field=)) -- the field's sum
+        # over the group's columns that hold a value and their number; None
+        # without an aggregate
         self.group, self.count = group, int(count)
+        self.sum = None if sum is None else int(sum)
+        self.sum_count = None if sum is None else int(sum_count or 0)
 
     def key(self):
         return tuple(g.row_id for g in self.group)
 
     def to_json(self):
-        return {"group": [g.to_json() for g in self.group], "count": self.count}
+        d = {"group": [g.to_json() for g in self.group], "count": self.count}
+        if self.sum is not None:
+            d["sum"] = self.sum
+            d["sumCount"] = self.sum_count
+        return d
 
     def __eq__(self, o):
-        return isinstance(o, GroupCount) and self.group == o.group and self.count == o.count
+        return isinstance(o, GroupCount) and self.group == o.group and self.count == o.count and \
+            self.sum == o.sum and self.sum_count == o.sum_count
 
     def __repr__(self):
-        return f"GroupCount({self.group}, {self.count})"
+        if self.sum is None:
+            return f"GroupCount({self.group}, {self.count})"
+        return f"GroupCount({self.group}, {self.count}, sum={self.sum}, sum_count={self.sum_count})"
 
 
 class QueryResponse:
@@ -209,7 +222,12 @@ def merge_group_counts(a: List[GroupCount], b: List[GroupCount], limit: int) -> 
         elif ka > kb:
             out.append(b[j]); j += 1
         else:
-            out.append(GroupCount(a[i].group, a[i].count + b[j].count)); i += 1; j += 1
+            x, y = a[i], b[j]
+            if x.sum is not None and y.sum is not None:
+                out.append(GroupCount(x.group, x.count + y.count, _wrap(x.sum + y.sum), x.sum_count + y.sum_count))
+            else:
+                out.append(GroupCount(x.group, x.count + y.count))
+            i += 1; j += 1
     while i < len(a) and len(out) < limit:
         out.append(a[i]); i += 1
     while j < len(b) and len(out) < limit:
@@ -1574,6 +1592,7 @@ class Executor:
         lim, has_lim = c.uint_arg("limit")
         limit = lim if has_lim else MAX_INT
         filt, _ = c.call_arg("filter")
+        self.group_by_aggregate(index, c)
         child_rows: List[Optional[List[int]]] = []
         for ch in c.children:
             if isinstance(ch.args.get("field"), str):
@@ -1601,6 +1620,31 @@ class Executor:
         if has_lim and limit < len(r):
             r = r[:limit]
         return r
+
+    def group_by_aggregate(self, index: str, c: Call):
+        """The validated ``aggregate=Sum(field=<int field>)`` of a GroupBy as
+        (field name, BSI group), or None without the argument.  Each returned
+        group then carries the field's sum over its columns (GroupCount.sum /
+        sum_count); which groups come back, and in what order, is unchanged."""
+        if "aggregate" not in c.args:
+            return None
+        agg = c.args["aggregate"]
+        if not isinstance(agg, Call):
+            raise PilosaError(f"GroupBy(): aggregate must be a call, but got {type(agg).__name__}")
+        if agg.name != "Sum":
+            raise PilosaError(f"GroupBy(): aggregate must be Sum(), but got {agg.name}()")
+        fname = agg.args.get("field")
+        if not fname:
+            raise PilosaError("Sum(): field required")
+        if agg.children:
+            raise PilosaError("Sum() inside aggregate= accepts no bitmap input, use GroupBy's filter=")
+        f = self.holder.field(index, fname) if isinstance(fname, str) else None
+        if f is None:
+            raise PilosaError(f"Sum(): field not found: {fname}")
+        b = f.bsi_group(fname)
+        if b is None:
+            raise PilosaError(f"Sum(): field {fname} is not an int field")
+        return fname, b
 
     def group_by_candidates(self, index: str, c: Call, shard: int, child_rows) -> Optional[List[List[int]]]:
         """Per field, the candidate row ids in this shard (None if a field's
@@ -1667,6 +1711,18 @@ class Executor:
         frags = [self.holder.fragment(index, f, VIEW_STANDARD, shard) for f in fields]
         results: List[GroupCount] = []
         k = len(fields)
+        agg = self.group_by_aggregate(index, c)
+        # a shard without the BSI fragment contributes 0 / 0 to every group
+        agg_frag = self.holder.fragment(index, agg[0], VIEW_BSI_PREFIX + agg[0], shard) if agg else None
+
+        def emit(key, cur: Row):
+            if agg is None:
+                return GroupCount([FieldRow(fields[i], key[i]) for i in range(k)], cur.count())
+            s = n = 0
+            if agg_frag is not None:
+                s, n = agg_frag.sum(cur, agg[1].bit_depth)
+            return GroupCount([FieldRow(fields[i], key[i]) for i in range(k)], cur.count(),
+                              _wrap(s + n * agg[1].base), n)
 
         def rec(level: int, acc: Optional[Row], prefix: Tuple[int, ...]):
             for rid in cands[level]:
@@ -1680,7 +1736,7 @@ class Executor:
                 if cur.is_empty():
                     continue
                 if level == k - 1:
-                    results.append(GroupCount([FieldRow(fields[i], key[i]) for i in range(k)], cur.count()))
+                    results.append(emit(key, cur))
                     if len(results) >= limit:
                         return True
                 else:
@@ -2014,7 +2070,7 @@ class Executor:
                         raise ErrFieldNotFound
                     key = ts.translate_row_to_string(index, fr.field, fr.row_id) if f.keys() else ""
                     grp.append(FieldRow(fr.field, fr.row_id, key))
-                out.append(GroupCount(grp, g.count))
+                out.append(GroupCount(grp, g.count, g.sum, g.sum_count))
             return out
         if c.name == "Rows" and isinstance(r, list):
             fname = c.args.get("_field")

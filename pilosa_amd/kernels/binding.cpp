@@ -346,6 +346,42 @@ void bsi_sum(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor 
   check_launch("bsi_sum");
 }
 
+// GroupBy(aggregate=Sum): out_sum[g] / out_cnt[g] += sum / count of group
+// program g (bsi_group_sum_kernel).  Returns the plane slabs run.
+int64_t bsi_group_sum(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor bsi_args,
+                      torch::Tensor out_sum, torch::Tensor out_cnt, int64_t planes, int64_t gchunk, int64_t fmode) {
+  check_dev(progs, "progs");
+  check_dev(views, "views");
+  check_dev(out_sum, "out_sum");
+  check_dev(out_cnt, "out_cnt");
+  TORCH_CHECK(!bsi_args.is_cuda() && bsi_args.scalar_type() == torch::kInt64 && bsi_args.numel() == 67,
+              "bsi_args must be a cpu int64[67]: view, depth, exists, sign, bit_row[63]");
+  TORCH_CHECK(progs.numel() % int64_t(sizeof(pk::QueryProg)) == 0, "progs must hold whole programs");
+  const int64_t G = progs.numel() / int64_t(sizeof(pk::QueryProg));
+  TORCH_CHECK(G < (int64_t(1) << 31) && S >= 0 && S < (int64_t(1) << 27), "bsi_group_sum: batch size");
+  TORCH_CHECK(out_sum.scalar_type() == torch::kInt64 && out_sum.numel() >= G, "out_sum must be int64[G]");
+  TORCH_CHECK(out_cnt.scalar_type() == torch::kInt64 && out_cnt.numel() >= G, "out_cnt must be int64[G]");
+  TORCH_CHECK(views.numel() % int64_t(sizeof(pk::ViewDev)) == 0, "views must hold whole ViewDev records");
+  auto a = bsi_args.data_ptr<int64_t>();
+  pk::BsiArgs b{};
+  b.view = int32_t(a[0]);
+  b.depth = int32_t(a[1]);
+  TORCH_CHECK(b.depth >= 0 && b.depth <= 63, "bsi depth");
+  TORCH_CHECK(a[0] >= 0 && a[0] < views.numel() / int64_t(sizeof(pk::ViewDev)), "bsi view slot");
+  TORCH_CHECK(planes >= 1 && planes <= 64 && gchunk >= 1 && gchunk < (int64_t(1) << 31), "bsi_group_sum: slab / chunk");
+  b.row_exists = a[2];
+  b.row_sign = a[3];
+  for (int i = 0; i < 64; i++) b.bit_row[i] = i < 63 ? a[4 + i] : -1;
+  const int nslab = pk::launch_bsi_group_sum(
+      reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), int(G),
+      reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b, int(planes), int(gchunk),
+      int(fmode), reinterpret_cast<unsigned long long*>(out_sum.data_ptr<int64_t>()),
+      reinterpret_cast<unsigned long long*>(out_cnt.data_ptr<int64_t>()), cur_stream(progs));
+  TORCH_CHECK(nslab >= 0, "bsi_group_sum: grid too large");
+  check_launch("bsi_group_sum");
+  return nslab;
+}
+
 void and2_count(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor pairs, torch::Tensor partial,
                 int64_t cq, int64_t variant) {
   check_dev(progs, "progs");
@@ -1146,6 +1182,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("densify", &densify, "dense bit rows of an arena over a shard range");
   m.def("block_hash", &block_hash, "anti-entropy: position count and XXH64 of (fragment, 100-row block) units");
   m.def("block_dump", &block_dump, "anti-entropy: one block's positions in ascending order");
+  m.def("bsi_group_sum", &bsi_group_sum, "per-group BSI sums: group programs streamed past LDS-staged planes",
+        py::arg("progs"), py::arg("views"), py::arg("S"), py::arg("bsi_args"), py::arg("out_sum"),
+        py::arg("out_cnt"), py::arg("planes"), py::arg("gchunk") = 64, py::arg("fmode") = 2);
   m.def("bsi_sum", &bsi_sum, "bit-sliced integer sum with optional filter program", py::arg("progs"),
         py::arg("views"), py::arg("S"), py::arg("bsi_args"), py::arg("out_sum"), py::arg("out_cnt"),
         py::arg("fmode") = 2);

@@ -962,6 +962,186 @@ __global__ __launch_bounds__(256) void bsi_sum_keys_kernel(const QueryProg* __re
   }
 }
 
+// BSI sum per group (GroupBy(..., aggregate=Sum(field=))): G filter programs
+// -- one per group, the GroupBy filter followed by the group's rows as a left
+// AND-fold -- over one BSI field.  bsi_sum_keys_kernel gives every (shard,
+// key, group) wave its own pass over all depth+2 plane tiles and decodes array
+// and run planes through LDS each time.  Here one workgroup owns one (shard,
+// key, plane slab, chunk of groups): its four waves stage exists, sign and the
+// slab's planes once into a block-shared LDS slab, in the per-lane Tile layout
+// (ulong2 at [i*64 + lane], so a read-back is eight conflict-free 16-byte LDS
+// reads), then stream the chunk's groups past them round-robin.  A group that
+// misses a leaf at this key costs no tile; one that is empty after the AND
+// with exists costs no plane.  The only barrier is the __syncthreads() after
+// staging; a workgroup whose key has no exists container leaves before it
+// (wave- and block-uniform).  Every wave adds its (group, unit) result with
+// one 64-bit atomic per output word, out_cnt from slab 0 only; zeros are
+// skipped.
+//
+// Measured (profiles/groupby_sum/README.md: 64 shards, depth 20, bitmap planes)
+// it moves 59 times fewer plane tiles than bsi_sum_keys_kernel at 1,024 groups
+// and still takes 1.2 - 1.3 times as long at 8, 32 and 1,024 groups: one
+// workgroup per CU and an unoverlapped chain of dependent loads per group,
+// repeated per slab.  GpuExecutor therefore routes to it only on request
+// (PILOSA_GROUPSUM_MIN_GROUPS).
+//
+// LDS: four WaveScratch (40 KiB, static) + (2 + planes) * 8 KiB dynamic; the
+// 160 KiB of a CU bound planes at GS_MAX_PLANES = 13 (one workgroup per CU), 3
+// planes still fit two workgroups.
+//
+// Resource usage (hipcc -O3 --offload-arch=gfx950
+// -Rpass-analysis=kernel-resource-usage):
+//   FMODE 1 (flat folds):  172 VGPRs, 0 AGPRs, 84 SGPRs, scratch 0, static LDS
+//                          40960 B, occupancy 2 waves/SIMD by registers
+//   FMODE 2 (any program): 256 VGPRs, 38 AGPRs, 84 SGPRs, scratch 0, static LDS
+//                          40960 B, occupancy 1 wave/SIMD
+// The slab is a native 16-byte vector (u64x2, moved as ds_*_b128), not ulong2:
+// copying Tile words to LDS as HIP vector structs left the staged tile in
+// 144 B/lane of scratch.
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+
+// candidate_mask for the one key j, read from the meta table build_slots left
+// in LDS: inside a loop over groups the mask[] array it indexes by opcode
+// would live in scratch memory
+__device__ __forceinline__ bool candidate_at(const QueryProg& qp, const WaveScratch& ws, int j) {
+  bool s0 = false, s1 = false, s2 = false, s3 = false;  // s0 = top
+  for (int pc = 0; pc < qp.nprog; pc++) {
+    const int op = qp.prog[pc];
+    if (op < OP_AND) {
+      s3 = s2; s2 = s1; s1 = s0; s0 = ws.meta[op][j] >= 0;
+    } else {
+      bool r;
+      if (op == OP_AND) r = s1 && s0;
+      else if (op == OP_ANDNOT) r = s1;
+      else r = s1 || s0;  // OR, XOR
+      s0 = r; s1 = s2; s2 = s3; s3 = false;
+    }
+  }
+  return s0;
+}
+
+template <int FMODE>
+__global__ __launch_bounds__(256) void bsi_group_sum_kernel(const QueryProg* __restrict__ progs, int G,
+                                                            const ViewDev* __restrict__ views, int S, BsiArgs bsi,
+                                                            int planes, int nslab, int gchunk, int nchunk,
+                                                            unsigned long long* __restrict__ out_sum,
+                                                            unsigned long long* __restrict__ out_cnt) {
+  __shared__ WaveScratch scratch[WAVES_PER_BLOCK];
+  extern __shared__ u64x2 gs_slab[];  // [2 + planes][512]: exists, sign, planes of the slab
+  const uint32_t unit = xcd_remap(blockIdx.x, gridDim.x);
+  const int wave = threadIdx.x >> 6;
+  const int lane = wave_lane();
+  const int chunk = int(unit % uint32_t(nchunk));
+  const int slab = int((unit / uint32_t(nchunk)) % uint32_t(nslab));
+  const int j = int((unit / (uint32_t(nchunk) * uint32_t(nslab))) & 15);
+  const int s = int(unit / (uint32_t(nchunk) * uint32_t(nslab) * 16));
+  if (s >= S) return;
+  WaveScratch& ws = scratch[wave];
+  const ViewDev& bv = views[bsi.view];
+  const uint32_t* rp = bv.rowptr + int64_t(s) * (bv.D + 1);
+  const int64_t base = bv.shard_base[s];
+  // container index of dense row d at key j (or -1), evaluated per lane
+  auto lane_find = [&](int64_t d) -> int64_t {
+    if (d < 0) return -1;
+    const int64_t lo = base + rp[d], hi = base + rp[d + 1];
+    if (hi - lo == 16) return lo + j;   // every key present (dense planes): no meta walk
+    for (int64_t c = lo; c < hi; c++)
+      if (meta_j(bv.meta[c]) == j) return c;
+    return -1;
+  };
+  // every wave resolves the same containers (lane i: plane i; then lanes 0 / 1:
+  // exists / sign), so the staging split needs no exchange between waves
+  const int p0 = slab * planes;
+  const int np = min(planes, bsi.depth - p0);  // planes of this slab (<= 0: none, depth 0)
+  const int64_t mine = (lane >= p0 && lane < p0 + np) ? lane_find(bsi.bit_row[lane]) : -1;
+  const int64_t extra = lane == 0 ? lane_find(bsi.row_exists) : (lane == 1 ? lane_find(bsi.row_sign) : -1);
+  const int64_t ce = rl_i64(extra, 0);
+  if (ce < 0) return;
+  const int64_t cs = rl_i64(extra, 1);
+  const uint64_t present = __ballot(mine >= 0);
+  // stage: wave w decodes tiles w, w+4, ... (0 exists, 1 sign, 2+p plane p0+p)
+  for (int t = wave; t < 2 + np; t += WAVES_PER_BLOCK) {
+    const int64_t ci = t == 0 ? ce : (t == 1 ? cs : rl_i64(mine, p0 + t - 2));
+    if (ci < 0) continue;  // absent: never read back
+    Tile tl;
+    tile_load(tl, bv.payload, bv.meta[ci], ws.lb);
+#pragma unroll
+    for (int i = 0; i < 8; i++) gs_slab[t * 512 + i * 64 + lane] = u64x2{tl.w[i].x, tl.w[i].y};
+  }
+  __syncthreads();
+  const int g1 = min(G, (chunk + 1) * gchunk);
+  for (int g = chunk * gchunk + wave; g < g1; g += WAVES_PER_BLOCK) {
+    const QueryProg& qp = progs[g];
+    Tile consider;
+    if (qp.nprog) {
+      uint32_t mask[MAXLEAF];
+      build_slots(qp, views, s, ws, mask);
+      if (!candidate_at(qp, ws, j)) continue;
+      if (FMODE == 1) eval_flat(qp, views, s, j, ws, consider);
+      else eval_tile(qp, views, s, j, ws, consider);
+      uint64_t any = 0;
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const u64x2 e = gs_slab[i * 64 + lane];
+        consider.w[i].x &= e.x;
+        consider.w[i].y &= e.y;
+        any |= consider.w[i].x | consider.w[i].y;
+      }
+      if (!__ballot(any != 0)) continue;
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const u64x2 e = gs_slab[i * 64 + lane];
+        consider.w[i] = make_ulong2(e.x, e.y);
+      }
+    }
+    const int64_t acc_cnt = slab == 0 ? tile_popc(consider) : 0;
+    // split once by sign (consider <- non-negative, sign <- negative columns);
+    // a key without a negative column counts one AND + popcount per plane word
+    Tile sign;
+    bool neg = false;
+    if (cs >= 0 && np > 0) {
+      uint64_t anyneg = 0;
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const ulong2 c = consider.w[i];
+        const u64x2 sg = gs_slab[512 + i * 64 + lane];
+        consider.w[i] = make_ulong2(c.x & ~sg.x, c.y & ~sg.y);
+        sign.w[i] = make_ulong2(c.x & sg.x, c.y & sg.y);
+        anyneg |= sign.w[i].x | sign.w[i].y;
+      }
+      neg = __ballot(anyneg != 0) != 0;
+    }
+    int64_t acc_sum = 0;
+    for (int p = 0; p < np; p++) {
+      if (!((present >> (p0 + p)) & 1)) continue;
+      const u64x2* pl = gs_slab + (2 + p) * 512 + lane;
+      int pc = 0, nc = 0;
+      if (neg) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          const u64x2 b = pl[i * 64];
+          pc += __popcll(b.x & consider.w[i].x) + __popcll(b.y & consider.w[i].y);
+          nc += __popcll(b.x & sign.w[i].x) + __popcll(b.y & sign.w[i].y);
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+          const u64x2 b = pl[i * 64];
+          pc += __popcll(b.x & consider.w[i].x) + __popcll(b.y & consider.w[i].y);
+        }
+      }
+      acc_sum += int64_t(uint64_t(int64_t(pc - nc)) << (p0 + p));
+    }
+    const int64_t tsum = wave_sum_i64(acc_sum);
+    const int64_t tcnt = wave_sum_i64(acc_cnt);
+    if (lane == 0) {
+      if (tsum) atomicAdd(out_sum + g, (unsigned long long)tsum);
+      if (tcnt) atomicAdd(out_cnt + g, (unsigned long long)tcnt);
+    }
+  }
+}
+
 // ---------------------------------------------------------------- BSI range
 // Bit-sliced comparators (O'Neil), reference fragment.go:1271-1534, with the
 // exact control flow of pilosa_amd/models/fragment.py (_range_eq/_lt/_gt/
@@ -1819,6 +1999,34 @@ void launch_bsi_sum(const QueryProg* progs, int Q, const ViewDev* views, int S, 
     hipLaunchKernelGGL(bsi_sum_keys_kernel<1>, grid, block, 0, st, progs, Q, views, S, bsi, out_sum, out_cnt);
   else
     hipLaunchKernelGGL(bsi_sum_keys_kernel<2>, grid, block, 0, st, progs, Q, views, S, bsi, out_sum, out_cnt);
+}
+
+int launch_bsi_group_sum(const QueryProg* progs, int G, const ViewDev* views, int S, BsiArgs bsi, int planes,
+                         int gchunk, int fmode, unsigned long long* out_sum, unsigned long long* out_cnt,
+                         hipStream_t st) {
+  if (G <= 0 || S <= 0) return 0;
+  planes = planes < 1 ? 1 : (planes > GS_MAX_PLANES ? GS_MAX_PLANES : planes);
+  if (bsi.depth < 1) planes = 1;
+  else if (planes > bsi.depth) planes = bsi.depth;
+  const int nslab = bsi.depth > 0 ? (bsi.depth + planes - 1) / planes : 1;
+  gchunk = gchunk < 1 ? 1 : gchunk;
+  const int nchunk = (G + gchunk - 1) / gchunk;
+  const int64_t blocks = int64_t(S) * 16 * nslab * nchunk;
+  if (blocks >= (int64_t(1) << 31)) return -1;
+  const int lds = (2 + planes) * 8192;
+  const dim3 grid{unsigned(blocks)}, block(64 * WAVES_PER_BLOCK);
+  if (fmode == 1) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bsi_group_sum_kernel<1>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(bsi_group_sum_kernel<1>, grid, block, lds, st, progs, G, views, S, bsi, planes, nslab, gchunk,
+                       nchunk, out_sum, out_cnt);
+  } else {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bsi_group_sum_kernel<2>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(bsi_group_sum_kernel<2>, grid, block, lds, st, progs, G, views, S, bsi, planes, nslab, gchunk,
+                       nchunk, out_sum, out_cnt);
+  }
+  return nslab;
 }
 
 }  // namespace pk

@@ -123,6 +123,16 @@ void launch_bsi_kth_step(const ViewDev* views, int S, BsiArgs bsi, uint64_t* can
 // fmode: 0 no filters, 1 flat-fold filter programs, 2 any program.
 void launch_bsi_sum(const QueryProg* progs, int Q, const ViewDev* views, int S, BsiArgs bsi,
                     unsigned long long* out_sum, unsigned long long* out_cnt, int fmode, hipStream_t st);
+// GroupBy(..., aggregate=Sum(field=)): out_sum[g] / out_cnt[g] += the BSI sum
+// (base-relative) / column count of group program g, G programs past LDS-staged
+// planes (bsi_group_sum_kernel).  planes = bit planes per LDS slab (clamped to
+// 1 .. GS_MAX_PLANES and to the depth), gchunk = groups per workgroup, fmode
+// 1 = every program is a flat fold, 2 = any program.  Returns the slabs run,
+// -1 when the grid would not fit.
+constexpr int GS_MAX_PLANES = 13;
+int launch_bsi_group_sum(const QueryProg* progs, int G, const ViewDev* views, int S, BsiArgs bsi, int planes,
+                         int gchunk, int fmode, unsigned long long* out_sum, unsigned long long* out_cnt,
+                         hipStream_t st);
 
 // Device TopN slot index (topn_kernels.hip): pass 1 counts cached-row bits per
 // column into colcnt[S*2^20]; pass 2 (fill) scatters cache slots behind the

@@ -2113,3 +2113,45 @@ class GpuEngine:
                 fmode = 2
             self.ext.bsi_sum(tp, tv, bsi_view.S, torch.from_numpy(args), out_sum, out_cnt, fmode)
         return out_sum, out_cnt
+
+    # bit planes per LDS slab of bsi_group_sum_kernel (1 .. 13: exists, sign and
+    # the slab's planes share one CU's LDS with the waves' scratch) and groups
+    # per workgroup; PILOSA_GROUPSUM_SLAB / PILOSA_GROUPSUM_CHUNK override them
+    # per call
+    GROUPSUM_SLAB = 13
+    GROUPSUM_CHUNK = 64
+
+    def bsi_group_sum(self, progs: np.ndarray, views: List["DeviceView"], bsi_view: "DeviceView", depth: int,
+                      per_filter: bool = False):
+        """Sum / count of a BSI field under each of G group programs
+        (GroupBy(..., aggregate=Sum(field=))): QPROG_DTYPE records whose leaf
+        views index ``views``; (sum int64[G], count int64[G]) on the device,
+        base-relative like bsi_sum_async.  One bsi_group_sum launch: the
+        planes of a (shard, key) are staged once per workgroup in LDS and the
+        groups streamed past them.  ``per_filter``: the same programs through
+        the per-filter kernel (bsi_sum_keys_kernel, one wave per (shard, key,
+        group)) instead.  Either way device memory is the programs plus two
+        int64 per group."""
+        torch = self.torch
+        G = len(progs)
+        outs = torch.zeros(2 * G, dtype=torch.int64, device=self.device)
+        out_sum, out_cnt = outs[:G], outs[G:]
+        S = bsi_view.S
+        if any(v.S != S for v in views):
+            raise CompileError("views in one batch must share the local shard list")
+        slot = next((i for i, v in enumerate(views) if v is bsi_view), len(views))
+        ordered = list(views) + ([bsi_view] if slot == len(views) else [])
+        args = self.bsi_args(bsi_view, depth, slot)
+        if not G or not S or args[2] < 0:
+            return out_sum, out_cnt
+        planes = int(os.environ.get("PILOSA_GROUPSUM_SLAB") or self.GROUPSUM_SLAB)
+        gchunk = int(os.environ.get("PILOSA_GROUPSUM_CHUNK") or self.GROUPSUM_CHUNK)
+        nprog = progs["nprog"]
+        fmode = 1 if bool(((nprog <= 1) | flat_mask(progs)).all()) else 2
+        tp, tv = self.upload_batch(progs, ordered)
+        if per_filter:
+            self.ext.bsi_sum(tp, tv, S, torch.from_numpy(args), out_sum, out_cnt, fmode)
+        else:
+            self.ext.bsi_group_sum(tp, tv, S, torch.from_numpy(args), out_sum, out_cnt, max(1, min(planes, 13)),
+                                   max(1, gchunk), fmode)
+        return out_sum, out_cnt

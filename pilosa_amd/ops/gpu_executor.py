@@ -14,7 +14,8 @@ device arenas of the involved field-views:
                 histogram + in-kernel heap walk (ops/topn_index.py); while
                 that index is stale: per-shard pair counts + the reference
                 heap semantics replayed on host (fragment.top)
-* ``group_by``  GroupBy(Rows..., filter)               -> batched k-way counts
+* ``group_by``  GroupBy(Rows..., filter)               -> batched k-way counts;
+                aggregate=Sum(field=f) -> bsi_group_sum over the final groups
 
 Arenas are (re)built lazily from the host fragments and cached per
 (index, field, view, shard list); every fragment carries a ``version`` that is
@@ -46,6 +47,12 @@ from .device import CompileError, DeviceView, GpuEngine, Leaf, Op
 MAX_GROUPS_PER_LAUNCH = 1 << 16
 # two-field GroupBy with at least this many row pairs runs as one count matrix
 GROUPBY_MATRIX_MIN = int(os.environ.get("PILOSA_GROUPBY_MATRIX_MIN", "1024"))
+# GroupBy(aggregate=Sum): final group lists of at least this many groups take
+# bsi_group_sum_kernel, shorter ones the per-filter kernel.  None = never: at
+# 8, 32 and 1,024 groups over 64 shards bsi_group_sum_kernel took 1.2 - 1.3
+# times as long (profiles/groupby_sum/README.md), so no crossover is known.
+# PILOSA_GROUPSUM_MIN_GROUPS overrides it per call.
+GROUPSUM_MIN_GROUPS: Optional[int] = None
 # minimum spacing of device TopN index rebuilds per view (the reference
 # re-ranks its caches at most every 10 s too, cache.go:235-243)
 TOPN_INDEX_REBUILD_S = float(os.environ.get("PILOSA_TOPN_INDEX_REBUILD_S", "10"))
@@ -165,6 +172,8 @@ class GpuExecutor:
         self._bsi_views: Dict[Tuple, DeviceView] = {}  # predicate results (small LRU)
         self.mu = threading.RLock()
         self.launches = 0
+        self.group_sum_device = 0   # GroupBy(aggregate=Sum) calls answered by bsi_group_sum_kernel
+        self.group_sum_per_filter = 0   # ... and by the per-filter kernel
         self.percentile_device = 0       # Percentile() calls answered by bsi_percentile (the fast path)
         # serving Count text path: host prep (parse..launch) vs result wait
         self.text_batches = 0
@@ -385,7 +394,8 @@ class GpuExecutor:
                 "launches": self.launches, "rebuilds": self.rebuilds, "shardUpdates": self.shard_updates,
                 "rowUpdates": self.row_updates, "deviceWrites": self.device_writes,
                 "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
-                "percentileDevice": self.percentile_device}
+                "percentileDevice": self.percentile_device, "groupSumDevice": self.group_sum_device,
+                "groupSumPerFilter": self.group_sum_per_filter}
 
     def invalidate(self):
         with self.mu:
@@ -1842,6 +1852,9 @@ class GpuExecutor:
         k = len(c.children)
         if k == 0 or k + (1 if filt is not None else 0) > 16:
             raise NotImplementedError
+        agg = ex.group_by_aggregate(index, c)
+        if agg is not None and os.environ.get("PILOSA_GROUPSUM_DEVICE", "1") == "0":
+            raise NotImplementedError   # aggregate GroupBys answered by the host path
         fields = []
         arenas = []
         cand: List[List[int]] = []
@@ -1887,14 +1900,53 @@ class GpuExecutor:
             mat = pair_count_matrix(arenas[0], cand[0], arenas[1], cand[1],
                                     filt=(fexpr.view, fexpr.row) if fexpr is not None else None,
                                     chunk_bytes=self._groupby_budget() - len(cand[0]) * len(cand[1]) * 12)
-            return [GroupCount([FieldRow(fields[0], ra), FieldRow(fields[1], rb)], n)
-                    for ra, rb, n in emit_groups(cand[0], cand[1], mat,
-                                                 None if start is None else (start[0], start[1] - 1), limit)]
+            groups = [((ra, rb), n) for ra, rb, n in
+                      emit_groups(cand[0], cand[1], mat, None if start is None else (start[0], start[1] - 1), limit)]
+        else:
+            try:
+                groups = self._pruned_groups(arenas, cand, fexpr, start, limit)
+            except CompileError:
+                raise NotImplementedError
+        if agg is None or not groups:
+            return [GroupCount([FieldRow(fields[i], key[i]) for i in range(k)], n) for key, n in groups]
+        # the group list is final: one pass of per-group BSI sums over it
         try:
-            groups = self._pruned_groups(arenas, cand, fexpr, start, limit)
+            sums = self._group_sums(index, agg, arenas, [key for key, _ in groups], fexpr, shards)
         except CompileError:
             raise NotImplementedError
-        return [GroupCount([FieldRow(fields[i], key[i]) for i in range(k)], n) for key, n in groups]
+        return [GroupCount([FieldRow(fields[i], key[i]) for i in range(k)], n, sm, sc)
+                for (key, n), (sm, sc) in zip(groups, sums)]
+
+    def _group_sums(self, index: str, agg, arenas, keys: List[Tuple[int, ...]], fexpr, shards):
+        """(sum, sum_count) of GroupBy's aggregate=Sum(field=) for every final
+        group key: the groups' AND-fold programs (the ones _count_keys counts),
+        at most MAX_GROUPS_PER_LAUNCH per launch.  From GROUPSUM_MIN_GROUPS
+        groups on they are streamed past the field's LDS-staged bit planes by
+        bsi_group_sum_kernel; below it (by default: always, see
+        profiles/groupby_sum/README.md) the per-filter kernel takes the same
+        programs.  A field without BSI data in these shards gives 0 / 0."""
+        import torch
+
+        from pilosa_amd.executor import _wrap
+        fname, b = agg
+        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
+        if bv is None:
+            return [(0, 0)] * len(keys)
+        env = os.environ.get("PILOSA_GROUPSUM_MIN_GROUPS")
+        min_groups = int(env) if env else GROUPSUM_MIN_GROUPS
+        per_filter = min_groups is None or len(keys) < min_groups
+        out: List[Tuple[int, int]] = []
+        for i in range(0, len(keys), MAX_GROUPS_PER_LAUNCH):
+            progs, views = self._key_programs(arenas, keys[i:i + MAX_GROUPS_PER_LAUNCH], fexpr)
+            self.launches += 1
+            s_t, n_t = self.engine.bsi_group_sum(progs, views, bv, b.bit_depth, per_filter=per_filter)
+            both = self.engine.to_host(torch.cat([s_t, n_t])).view(2, -1)
+            out.extend((_wrap(int(sv) + int(nv) * b.base), int(nv)) for sv, nv in zip(*both.tolist()))
+        if per_filter:
+            self.group_sum_per_filter += 1
+        else:
+            self.group_sum_device += 1
+        return out
 
     # HBM the two-field count matrix may use (densified rows + the matrix)
     GROUPBY_HBM = int(os.environ.get("PILOSA_GROUPBY_HBM", str(8 << 30)))
@@ -1969,10 +2021,19 @@ class GpuExecutor:
         built column-wise with numpy (a left AND-fold over the leaves) instead
         of one expression object per key; a non-leaf filter goes through the
         expression compiler."""
+        eng = self.engine
+        progs, views = self._key_programs(arenas, keys, fexpr)
+        return eng.launch_count(eng.prepare_progs(progs, views, views[0].S)).cpu().numpy()
+
+    def _key_programs(self, arenas, keys: List[Tuple[int, ...]], fexpr):
+        """(QPROG_DTYPE records, their views in slot order) of filter & row_0 &
+        ... & row_l for every key of one level (shared by the counts of the
+        pruned walk and the per-group sums)."""
         from .device import OP_AND, QPROG_DTYPE
         if fexpr is not None and type(fexpr) is not Leaf:
             exprs = [Op("and", (fexpr, *[Leaf(arenas[x], key[x]) for x in range(len(key))])) for key in keys]
-            return self.engine.count(exprs)
+            progs, views, _ = self.engine.compile_batch(exprs)
+            return progs, views
         L0 = 1 if fexpr is not None else 0
         lvl = len(keys[0])
         L = L0 + lvl
@@ -1997,8 +2058,7 @@ class GpuExecutor:
             progs["leaf_row"][:, L0 + x] = arenas[x].dense_many(kk[:, x])
         pg = [0] + [v for i in range(1, L) for v in (i, OP_AND)]
         progs["prog"][:, :len(pg)] = np.asarray(pg, np.uint8)
-        eng = self.engine
-        return eng.launch_count(eng.prepare_progs(progs, views, views[0].S)).cpu().numpy()
+        return progs, views
 
     @staticmethod
     def _next_rows(rows: List[int], prefix: Tuple[int, ...], start: Optional[Tuple[int, ...]]) -> List[int]:

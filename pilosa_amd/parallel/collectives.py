@@ -628,8 +628,10 @@ def _default(o):
     if isinstance(o, ValCount):
         return msgpack.ExtType(_EXT_VALCOUNT, msgpack.packb([int(o.val), int(o.count)]))
     if isinstance(o, GroupCount):
-        return msgpack.ExtType(_EXT_GROUPCOUNT, msgpack.packb([[_default(g) for g in o.group], int(o.count)],
-                                                              default=_default))
+        body = [[_default(g) for g in o.group], int(o.count)]
+        if o.sum is not None:   # GroupBy(aggregate=Sum): two more members
+            body += [int(o.sum), int(o.sum_count)]
+        return msgpack.ExtType(_EXT_GROUPCOUNT, msgpack.packb(body, default=_default))
     if isinstance(o, RowIdentifiers):
         return msgpack.ExtType(_EXT_ROWIDS, msgpack.packb([list(o.rows), o.keys]))
     if isinstance(o, FieldRow):
@@ -665,7 +667,7 @@ def _ext_hook(code, data):
     if code == _EXT_VALCOUNT:
         return ValCount(v[0], v[1])
     if code == _EXT_GROUPCOUNT:
-        return GroupCount(list(v[0]), v[1])
+        return GroupCount(list(v[0]), v[1], *v[2:4])
     if code == _EXT_ROWIDS:
         return RowIdentifiers(v[0], v[1])
     if code == _EXT_FIELDROW:
@@ -702,6 +704,9 @@ def decode(data: bytes):
 # internal/public.proto, reduced by executor.go mapReduce).
 (TAG_NONE, TAG_MSGPACK, TAG_VALCOUNT, TAG_PAIR, TAG_PAIRS, TAG_ROWIDS, TAG_GROUPS, TAG_ROW,
  TAG_INT, TAG_BOOL, TAG_DEVROW) = range(11)
+# group lists of GroupBy(aggregate=Sum): TAG_GROUPS' layout with k + 3 columns
+# per group (rows, count, sum, sum_count)
+TAG_GROUPS_SUM = 11
 
 
 def encode_row_block(blk, device):
@@ -773,6 +778,13 @@ def encode_partial(obj) -> np.ndarray:
         if all(len(g.group) == k and all(fr.field == f and not fr.row_key for fr, f in zip(g.group, fields))
                for g in obj):
             names = encode(fields)
+            if all(g.sum is not None for g in obj):
+                mat = np.array([[fr.row_id for fr in g.group] + [g.count, g.sum & ((1 << 64) - 1), g.sum_count]
+                                for g in obj], np.uint64).view(np.int64)
+                return np.concatenate([np.array([TAG_GROUPS_SUM, len(obj), k, len(names)], np.int64),
+                                       _bytes_to_words(names), mat.reshape(-1)])
+            if any(g.sum is not None for g in obj):
+                return msg()
             mat = np.array([[fr.row_id for fr in g.group] + [g.count] for g in obj], np.uint64).view(np.int64)
             return np.concatenate([np.array([TAG_GROUPS, len(obj), k, len(names)], np.int64), _bytes_to_words(names),
                                    mat.reshape(-1)])
@@ -828,6 +840,14 @@ def decode_partial(w: np.ndarray):
         fields = decode(_words_to_bytes(w[4:4 + nw], nb))
         mat = w[4 + nw:4 + nw + n * (k + 1)].view(np.uint64).reshape(n, k + 1).tolist()
         return [GroupCount([FieldRow(f, r) for f, r in zip(fields, row[:k])], row[k]) for row in mat]
+    if tag == TAG_GROUPS_SUM:
+        n, k, nb = int(w[1]), int(w[2]), int(w[3])
+        nw = (nb + 7) // 8
+        fields = decode(_words_to_bytes(w[4:4 + nw], nb))
+        body = w[4 + nw:4 + nw + n * (k + 3)].reshape(n, k + 3)
+        rows = body[:, :k + 1].view(np.uint64).tolist()
+        return [GroupCount([FieldRow(f, r) for f, r in zip(fields, row[:k])], row[k], int(sm), int(sc))
+                for row, sm, sc in zip(rows, body[:, k + 1].tolist(), body[:, k + 2].tolist())]
     if tag == TAG_DEVROW:
         from pilosa_amd.ops.device import GpuEngine
         from pilosa_amd.ops.gpu_executor import row_from_bitmaps

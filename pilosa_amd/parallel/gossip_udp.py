@@ -171,6 +171,13 @@ class UdpProber:
                 if node is None:     # only members are probed for a peer
                     self.dropped += 1
                     continue
+                me = next((n for n in self.members() if n.id == self.node_id), None)
+                if me is not None and self.addr_of(node) == self.addr_of(me):
+                    # the target shares this node's gossip address (one host, one
+                    # port): the relayed PING would come back to this socket and
+                    # be acknowledged by this node itself
+                    self.dropped += 1
+                    continue
                 mine = self._next_seq()
                 with self._mu:
                     self._relay[mine] = (addr, seq)

@@ -128,6 +128,9 @@ def result_to_pb(r: Any, call_name: str = ""):
         m.Type = QUERY_RESULT_TYPE_GROUPCOUNTS
         for g in r:
             gc = m.GroupCounts.add(Count=g.count)
+            if g.sum is not None:
+                # HasSum tells a sum of 0 from "no aggregate"
+                gc.Sum, gc.SumCount, gc.HasSum = g.sum, g.sum_count, True
             for fr in g.group:
                 gc.Group.add(Field=fr.field, RowID=fr.row_id, RowKey=fr.row_key)
     elif isinstance(r, list):
@@ -165,7 +168,8 @@ def result_from_pb(m):
     if t == QUERY_RESULT_TYPE_ROWIDS:
         return list(m.RowIDs)
     if t == QUERY_RESULT_TYPE_GROUPCOUNTS:
-        return [GroupCount([FieldRow(g.Field, g.RowID, g.RowKey) for g in gc.Group], gc.Count)
+        return [GroupCount([FieldRow(g.Field, g.RowID, g.RowKey) for g in gc.Group], gc.Count,
+                           gc.Sum if gc.HasSum else None, gc.SumCount if gc.HasSum else None)
                 for gc in m.GroupCounts]
     raise ValueError(f"unknown result type {t}")
 

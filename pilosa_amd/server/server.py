@@ -620,8 +620,22 @@ class Server:
         reference's coordinator.  A DOWN node that answers again is READY."""
         from pilosa_amd.parallel.swim import DOWN, FailureDetector
         up = self.udp_prober
-        det = FailureDetector(self.node.id, up.ping if up is not None else self._swim_probe,
-                              up.ping_req if up is not None else self._swim_indirect,
+        # a peer whose gossip address is this node's own (several nodes on one
+        # host with one [gossip] port: only the first could bind it) is probed
+        # over its HTTP port: a UDP ping to it is answered by this node itself,
+        # so the peer would look alive for ever
+        own = self._gossip_addr(self.node)
+
+        def probe(node, timeout):
+            if up is None or self._gossip_addr(node) == own:
+                return self._swim_probe(node, timeout)
+            return up.ping(node, timeout)
+
+        def indirect(helper, target, timeout):
+            if up is None or own in (self._gossip_addr(helper), self._gossip_addr(target)):
+                return self._swim_indirect(helper, target, timeout)
+            return up.ping_req(helper, target, timeout)
+        det = FailureDetector(self.node.id, probe, indirect,
                               probe_interval=self.probe_interval, probe_timeout=self.probe_timeout,
                               suspicion_mult=self.suspicion_mult, indirect_checks=self.indirect_checks)
         self.failure_detector = det
