@@ -57,6 +57,12 @@ def nearest_rank(num: int, den: int, n: int) -> int:
     return max(1, -((-num * n) // den))
 
 
+def _topk_device() -> str:
+    """PILOSA_TOPK_DEVICE: "0" keeps TopK() on the host, "programs" / "kernel"
+    force one device route, anything else lets GpuExecutor.topk choose."""
+    return os.environ.get("PILOSA_TOPK_DEVICE", "")
+
+
 def _percentile_device() -> bool:
     return os.environ.get("PILOSA_PERCENTILE_DEVICE", _PERCENTILE_DEVICE_DEFAULT) not in ("0", "")
 
@@ -748,6 +754,8 @@ class Executor:
                 return None
             if n == "TopN":
                 return self._topn(index, c, shards, opt)
+            if n == "TopK":
+                return self._topk(index, c, shards, opt)
             if n == "Rows":
                 return self._rows(index, c, shards, opt)
             if n == "GroupBy":
@@ -1521,6 +1529,65 @@ class Executor:
                                    filter_values=attr_values, tanimoto_threshold=tanimoto,
                                    attr_store=f.row_attr_store if f is not None else None))
 
+    # ================================================================ TopK
+    def topk_params(self, index: str, c: Call):
+        """The validated (field name, k) of a TopK() call; k = 0: every row."""
+        for name in c.args:
+            if name not in ("field", "k"):
+                raise PilosaError(f'TopK(): unknown argument "{name}"')
+        fname = c.args.get("field")
+        if not isinstance(fname, str) or not fname:
+            raise PilosaError("TopK(): field required")
+        k = c.args.get("k", 0)
+        if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+            raise PilosaError("TopK(): k must be a non-negative integer")
+        if len(c.children) > 1:
+            raise PilosaError("TopK() only accepts a single bitmap input")
+        f = self.holder.field(index, fname)
+        if f is None:
+            raise ErrFieldNotFound
+        if f.type == FIELD_TYPE_INT:
+            raise PilosaError(f'cannot compute TopK() on integer field: "{fname}"')
+        return fname, k
+
+    def _topk(self, index: str, c: Call, shards, opt) -> List[Pair]:
+        """TopK(field=<set | mutex | bool | time field>, [k=<n>]) and
+        TopK(<one bitmap call>, field=, [k=]): the field's rows (standard view)
+        ranked by their exact count (an extension: Pilosa v1.3 has only the
+        approximate, cache-bound TopN).
+
+        The count of a row is |row ∩ filter| summed over all shards, |row|
+        without a filter; rows counting 0 are left out.  The order is count
+        descending, then row id ascending, cut to the first k (k absent or 0:
+        every row), so ties are deterministic.  No rank cache is read or
+        touched: fields with cacheType none work.
+
+        The map step emits every non-zero (row, count) of a shard -- on the
+        device one pass of row_filter_counts_kernel over the local shards
+        (GpuExecutor.topk) -- and the reduce adds them by row.  Only the
+        coordinating node sorts and cuts: a node answering a remote request
+        returns all its pairs, since exactness needs every partial."""
+        fname, k = self.topk_params(index, c)
+        local = (lambda ss: self.gpu.topk(index, c, ss)) if self.gpu is not None and _topk_device() != "0" else None
+        r = self.map_reduce(index, shards, c, opt, lambda s: self._topk_shard(index, c, fname, s),
+                            lambda p, v: pairs_add(p or [], v or []), local)
+        pairs = sort_pairs(r or [])
+        if opt.remote:
+            return pairs
+        return pairs[:k] if k else pairs
+
+    def _topk_shard(self, index: str, c: Call, fname: str, shard: int) -> List[Pair]:
+        frag = self.holder.fragment(index, fname, VIEW_STANDARD, shard)
+        if frag is None:
+            return []
+        filt = self.bitmap_call_shard(index, c.children[0], shard) if c.children else None
+        out = []
+        for rid in frag.rows():
+            n = frag.row_count(rid) if filt is None else frag.row(rid).intersection_count(filt)
+            if n > 0:
+                out.append(Pair(rid, n))
+        return out
+
     # ================================================================ Rows / GroupBy
     def _rows(self, index: str, c: Call, shards, opt) -> List[int]:
         if isinstance(c.args.get("field"), str):
@@ -2051,8 +2118,9 @@ class Executor:
                     return Pair(0, r.count, key)
             return r
         # a []Pair result -- TopN's, even empty (executor.go:2832-2846)
-        if isinstance(r, PairArray) or isinstance(r, list) and (c.name == "TopN" or (r and isinstance(r[0], Pair))):
-            fname = c.args.get("_field")
+        if isinstance(r, PairArray) or isinstance(r, list) and (c.name in ("TopN", "TopK") or
+                                                                (r and isinstance(r[0], Pair))):
+            fname = c.args.get("field") if c.name == "TopK" else c.args.get("_field")
             if isinstance(fname, str) and fname:
                 f = idx.field(fname)
                 if f is None:

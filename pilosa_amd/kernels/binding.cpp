@@ -1013,6 +1013,31 @@ void rows_list(torch::Tensor view, int64_t s0, int64_t ns, int64_t j, int64_t co
   check_launch("rows_list");
 }
 
+// TopK(field=, k=): out[d] += |row d of `view` ∩ dense row `filter_row` of
+// `filter`| over the S arena shards (row_filter_counts_kernel); `filter` an
+// empty tensor = no filter, out[d] += |row d|.  Returns the workgroups run.
+int64_t row_filter_counts(torch::Tensor view, torch::Tensor filter, int64_t filter_row, int64_t S, torch::Tensor out,
+                          int64_t rows_per_block, int64_t rows_per_wave) {
+  check_dev(out, "out");
+  const pk::ViewDev v = viewdev_from(view);
+  TORCH_CHECK(out.scalar_type() == torch::kInt64 && out.is_contiguous() && out.numel() >= v.D, "out int64[D]");
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 27) && v.D >= 0 && rows_per_block >= 0, "row_filter_counts sizes");
+  auto* o = reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>());
+  int64_t blocks;
+  if (filter.numel() == 0) {
+    blocks = pk::launch_row_filter_counts(v, nullptr, -1, int(S), rows_per_block, 0, o, cur_stream(out));
+  } else {
+    const pk::ViewDev x = viewdev_from(filter);
+    TORCH_CHECK(filter_row >= 0 && filter_row < x.D, "filter_row must be a dense row of the filter view");
+    blocks = pk::launch_row_filter_counts(v, &x, filter_row, int(S), rows_per_block,
+                                          int(rows_per_wave < 0 || rows_per_wave > 64 ? 0 : rows_per_wave), o,
+                                          cur_stream(out));
+  }
+  TORCH_CHECK(blocks >= 0, "row_filter_counts: grid too large");
+  check_launch("row_filter_counts");
+  return blocks;
+}
+
 void container_merge(torch::Tensor old_meta, torch::Tensor payload, torch::Tensor dstart, torch::Tensor dlows,
                      torch::Tensor dmeta, torch::Tensor dpayload, int64_t mode, bool clear, torch::Tensor scratch,
                      torch::Tensor card, torch::Tensor nruns) {
@@ -1176,6 +1201,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("src"), py::arg("S"), py::arg("n"), py::arg("main_out"), py::arg("main_meta"), py::arg("spill_out"),
         py::arg("spill_meta"), py::arg("M") = 1, py::arg("row_words") = 16384);
   m.def("rows_list", &rows_list, "flag dense rows with non-empty containers (optionally holding one column)");
+  m.def("row_filter_counts", &row_filter_counts,
+        "TopK: per-row intersection counts of a whole field with one LDS-staged filter row", py::arg("view"),
+        py::arg("filter"), py::arg("filter_row"), py::arg("S"), py::arg("out"), py::arg("rows_per_block") = 0,
+        py::arg("rows_per_wave") = 0);
   m.def("container_merge", &container_merge, "device write path: old container + delta -> bitmap + cardinality");
   m.def("payload_compact", &payload_compact, "copy live containers into a compacted payload buffer");
   m.def("container_emit", &container_emit, "device write path: bitmap -> final run/array/bitmap container (Optimize rule) + metadata");

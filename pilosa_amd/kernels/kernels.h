@@ -134,6 +134,18 @@ int launch_bsi_group_sum(const QueryProg* progs, int G, const ViewDev* views, in
                          int gchunk, int fmode, unsigned long long* out_sum, unsigned long long* out_cnt,
                          hipStream_t st);
 
+// TopK(field=, k=) (topk_kernels.hip, K25): out[d] += |row d ∩ filter| over
+// the S arena shards for every dense row d of ``fv``; the filter is dense row
+// ``xd`` of ``*xv`` (same shard list), staged once per (shard, key) in LDS.
+// xv == nullptr: no filter, out[d] += |row d| from the metadata alone.
+// rows_per_block > 0 splits the rows of a (shard, key) over several
+// workgroups, 0 = one workgroup per (shard, key); rows_per_wave = rows a wave
+// looks up per step (16, 32 or 64; anything else: chosen from the rows of a
+// workgroup).  out must hold fv.D words.
+// Returns the workgroups launched, -1 when the grid would not fit.
+int64_t launch_row_filter_counts(const ViewDev& fv, const ViewDev* xv, int64_t xd, int S, int64_t rows_per_block,
+                                 int rows_per_wave, unsigned long long* out, hipStream_t st);
+
 // Device TopN slot index (topn_kernels.hip): pass 1 counts cached-row bits per
 // column into colcnt[S*2^20]; pass 2 (fill) scatters cache slots behind the
 // per-shard exclusive scan colptr[S][2^20+1] (colcnt reused as cursors).

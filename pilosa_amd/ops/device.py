@@ -2155,3 +2155,35 @@ class GpuEngine:
             self.ext.bsi_group_sum(tp, tv, S, torch.from_numpy(args), out_sum, out_cnt, max(1, min(planes, 13)),
                                    max(1, gchunk), fmode)
         return out_sum, out_cnt
+
+    # rows of a (shard, key) per workgroup of row_filter_counts_kernel (0 = all
+    # of them, one workgroup per (shard, key)); PILOSA_TOPK_ROWS_PER_BLOCK
+    # overrides it per call.  PILOSA_TOPK_ROWS_PER_WAVE (16, 32, 64) fixes the
+    # rows a wave looks up per step; by default the launch picks it from the
+    # rows of a workgroup (profiles/topk/README.md)
+    TOPK_ROWS_PER_BLOCK = 2048
+
+    def row_filter_counts(self, view: "DeviceView", filt: Optional[Leaf] = None):
+        """|row ∩ filter| summed over the arena shards for EVERY dense row of
+        ``view`` (TopK): int64[D] on the device, one row_filter_counts launch.
+        ``filt``: a Leaf whose view shares ``view``'s shard list (staged once
+        per (shard, key) in LDS); None counts the rows themselves from the
+        metadata.  A filter row without containers gives zeros, no launch."""
+        torch = self.torch
+        out = torch.zeros(view.D, dtype=torch.int64, device=self.device)
+        if not view.D or not view.S:
+            return out
+        rpb = int(os.environ.get("PILOSA_TOPK_ROWS_PER_BLOCK") or self.TOPK_ROWS_PER_BLOCK)
+        if filt is None:
+            self.ext.row_filter_counts(view.viewdev_tensor(), torch.zeros(0, dtype=torch.uint8), -1, view.S, out, 0)
+            return out
+        fv = filt.view
+        if fv.S != view.S or tuple(fv.shards) != tuple(view.shards):
+            raise CompileError("views in one batch must share the local shard list")
+        xd = fv.dense(filt.row)
+        if xd < 0:
+            return out
+        view.ensure_keymask()
+        rpw = int(os.environ.get("PILOSA_TOPK_ROWS_PER_WAVE") or 0)
+        self.ext.row_filter_counts(view.viewdev_tensor(), fv.viewdev_tensor(), xd, view.S, out, max(0, rpb), rpw)
+        return out

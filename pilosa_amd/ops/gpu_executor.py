@@ -10,6 +10,8 @@ device arenas of the involved field-views:
 * ``bsi_sum``   Sum(<filter>, field=f)                -> bsi_sum kernel
 * ``bsi_percentile`` Percentile(<filter>, field=f, nth=p) -> bsi_kth_init +
                 one bsi_kth_step launch per bit (global MSB-first descent)
+* ``topk``      TopK(<filter>, field=f, k=n)           -> row_filter_counts (one
+                pass: filter staged per (shard, key), every row streamed past)
 * ``topn``      TopN phase-1/phase-2 with src          -> slot-index LDS
                 histogram + in-kernel heap walk (ops/topn_index.py); while
                 that index is stale: per-shard pair counts + the reference
@@ -53,6 +55,14 @@ GROUPBY_MATRIX_MIN = int(os.environ.get("PILOSA_GROUPBY_MATRIX_MIN", "1024"))
 # times as long (profiles/groupby_sum/README.md), so no crossover is known.
 # PILOSA_GROUPSUM_MIN_GROUPS overrides it per call.
 GROUPSUM_MIN_GROUPS: Optional[int] = None
+# TopK(): the device route taken when PILOSA_TOPK_DEVICE names none: "kernel"
+# (row_filter_counts_kernel) or "programs" (one program per row through
+# count_per_shard).  The kernel: on 64 shards it was ahead of or level with
+# the programs route at 64, 1,000, 10,000 and 50,000 rows on device time (0.20
+# against 0.25 ms at 64 rows, 1.36 against 113 ms at 50,000 rows under a dense
+# filter) and ahead everywhere once the per-row compilation of the programs
+# route counts (profiles/topk/README.md), so there is no crossover to route by.
+TOPK_DEFAULT_ROUTE = "kernel"
 # minimum spacing of device TopN index rebuilds per view (the reference
 # re-ranks its caches at most every 10 s too, cache.go:235-243)
 TOPN_INDEX_REBUILD_S = float(os.environ.get("PILOSA_TOPN_INDEX_REBUILD_S", "10"))
@@ -175,6 +185,8 @@ class GpuExecutor:
         self.group_sum_device = 0   # GroupBy(aggregate=Sum) calls answered by bsi_group_sum_kernel
         self.group_sum_per_filter = 0   # ... and by the per-filter kernel
         self.percentile_device = 0       # Percentile() calls answered by bsi_percentile (the fast path)
+        self.topk_device = 0             # TopK() map steps answered by row_filter_counts_kernel
+        self.topk_programs = 0           # ... and by the per-row programs route
         # serving Count text path: host prep (parse..launch) vs result wait
         self.text_batches = 0
         self.text_prep_s = 0.0
@@ -395,7 +407,8 @@ class GpuExecutor:
                 "rowUpdates": self.row_updates, "deviceWrites": self.device_writes,
                 "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
                 "percentileDevice": self.percentile_device, "groupSumDevice": self.group_sum_device,
-                "groupSumPerFilter": self.group_sum_per_filter}
+                "groupSumPerFilter": self.group_sum_per_filter, "topkDevice": self.topk_device,
+                "topkPrograms": self.topk_programs}
 
     def invalidate(self):
         with self.mu:
@@ -1258,6 +1271,74 @@ class GpuExecutor:
             except CompileError:
                 raise NotImplementedError   # src too large for one device program: host path
         return self._topn_pairs_path(rc, rv, src, n, ids, threshold)
+
+    def topk(self, index: str, c: Call, shards: List[int]) -> List[Pair]:
+        """TopK(<filter>, field=, k=)'s map step over the local shards: every
+        row of the field's standard view with its exact count |row ∩ filter|
+        (|row| without a filter) where that is not 0, uncut and unsorted -- the
+        executor adds the partials, sorts and cuts.
+
+        Two routes give the same numbers.  ``kernel``: one
+        row_filter_counts_kernel pass (the filter staged once per (shard, key)
+        in LDS, all rows streamed past it; a filter that is not a plain row is
+        evaluated once into a dense one-row view first), then nonzero + gather
+        on the device, so only the non-zero (dense row, count) pairs cross to
+        the host.  ``programs``: one Op("and", (filter, Leaf(field, row)))
+        program per row through count_per_shard, MAX_GROUPS_PER_LAUNCH per
+        launch (the route _topn_pairs_path and _count_keys use).
+        PILOSA_TOPK_DEVICE = kernel | programs forces one; the default is
+        TOPK_DEFAULT_ROUTE (profiles/topk/README.md)."""
+        import torch
+
+        ex = self._ex()
+        fname, _ = ex.topk_params(index, c)
+        route = os.environ.get("PILOSA_TOPK_DEVICE", "") or TOPK_DEFAULT_ROUTE
+        if route not in ("kernel", "programs"):
+            route = TOPK_DEFAULT_ROUTE
+        rv = self.view_arena(index, fname, VIEW_STANDARD, shards)
+        filt = None
+        if c.children:
+            filt = self.plan(index, c.children[0], shards)
+            if filt is not EMPTY and _has_shift(filt):
+                raise NotImplementedError   # a Shift spills into the next shard: host path
+        if rv is None or rv.D == 0 or rv.S == 0 or filt is EMPTY:
+            pairs: List[Pair] = []
+        elif route == "programs":
+            pairs = self._topk_programs(rv, filt)
+        else:
+            try:
+                if filt is not None and type(filt) is not Leaf:
+                    self.launches += 1
+                    filt = Leaf(self.engine.dense_view(filt), 0)
+                self.launches += 1
+                cnt = self.engine.row_filter_counts(rv, filt)
+            except CompileError:
+                raise NotImplementedError
+            nz = torch.nonzero(cnt).reshape(-1)
+            both = self.engine.to_host(torch.stack([nz, cnt[nz]])).tolist()
+            rows = rv.rows
+            pairs = [Pair(int(rows[d]), int(n)) for d, n in zip(*both)]
+        if route == "programs":
+            self.topk_programs += 1
+        else:
+            self.topk_device += 1
+        return pairs
+
+    def _topk_programs(self, rv: DeviceView, filt) -> List[Pair]:
+        """TopK's counts by the per-row programs route: filter & row for every
+        row of the view, at most MAX_GROUPS_PER_LAUNCH programs per launch."""
+        rows = [int(r) for r in rv.rows]
+        pairs: List[Pair] = []
+        try:
+            for i in range(0, len(rows), MAX_GROUPS_PER_LAUNCH):
+                part = rows[i:i + MAX_GROUPS_PER_LAUNCH]
+                exprs = [Leaf(rv, r) if filt is None else Op("and", (filt, Leaf(rv, r))) for r in part]
+                self.launches += 1
+                tot = self.engine.count_per_shard(exprs).sum(axis=1)
+                pairs.extend(Pair(r, int(n)) for r, n in zip(part, tot.tolist()) if n > 0)
+        except CompileError:
+            raise NotImplementedError
+        return pairs
 
     def _plain_rc(self, index: str, fname: str, shards: List[int], key=None):
         """The field's standard view and rank caches over ``shards``, resolved

@@ -120,7 +120,7 @@ def result_to_pb(r: Any, call_name: str = ""):
         m.Type = QUERY_RESULT_TYPE_PAIRS
         for i, c in zip(r.ids.tolist(), r.counts.tolist()):
             m.Pairs.add(ID=i, Count=c)
-    elif isinstance(r, list) and (not r and call_name == "TopN" or r and isinstance(r[0], Pair)):
+    elif isinstance(r, list) and (not r and call_name in ("TopN", "TopK") or r and isinstance(r[0], Pair)):
         m.Type = QUERY_RESULT_TYPE_PAIRS
         for p in r:
             m.Pairs.add(ID=p.id, Key=p.key, Count=p.count)
