@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "device_util.h"
 
 namespace pk {
 namespace {
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(256) void densify_kernel(ViewDev v, const int64_t* 
     for (int i = 0; i < 8; i++) dst[i * 64 + lane] = make_ulong2(0, 0);
     return;
   }
-  const uint16_t* p = v.payload + meta_off16(m) * 8;
+  const uint16_t* p = payload_of(v, m);
   if (meta_type(m) == CT_BITMAP) {
     const ulong2* src = reinterpret_cast<const ulong2*>(p);
 #pragma unroll
@@ -343,7 +344,7 @@ __global__ __launch_bounds__(256) void densify_kernel(ViewDev v, const int64_t* 
   }
   uint64_t* lb = lbs[wave];
   for (int i = lane; i < 1024; i += 64) lb[i] = 0;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  lds_fence();
   if (meta_type(m) == CT_ARRAY) {
     const int n = meta_n(m);
     for (int i = lane; i < n; i += 64) {
@@ -358,7 +359,7 @@ __global__ __launch_bounds__(256) void densify_kernel(ViewDev v, const int64_t* 
         atomicOr(reinterpret_cast<unsigned long long*>(&lb[x >> 6]), 1ull << (x & 63));
     }
   }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  lds_fence();
   const ulong2* l2 = reinterpret_cast<const ulong2*>(lb);
 #pragma unroll
   for (int i = 0; i < 8; i++) dst[i * 64 + lane] = l2[i * 64 + lane];

@@ -88,7 +88,7 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
 // out_count != nullptr: only add the matching column count (no view is written).
 void launch_bsi_range(const ViewDev* views, int S, BsiArgs bsi, int op, int64_t p1, int64_t p2, uint16_t* out_payload,
                       int64_t* out_meta, unsigned long long* out_count, hipStream_t st);
-// BSI min/max descents per (shard, key): out int64[S*16*10] (see bitmap_kernels.hip).
+// BSI min/max descents per (shard, key): out int64[S*16*10] (see bsi_kernels.hip).
 // the [F fragments x G keys x 10] descents -> out int64[3] {value, count, found}
 // part: int64[4 * ceil(F / 64)] scratch of the multi-block fold (G == 16), or nullptr
 void launch_bsi_minmax_fold(const int64_t* o, int F, int G, int is_min, int64_t* out, int64_t* part,
@@ -96,7 +96,7 @@ void launch_bsi_minmax_fold(const int64_t* o, int F, int G, int is_min, int64_t*
 void launch_bsi_minmax(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int64_t* out,
                        hipStream_t st, int which = 0);
 // Percentile(field=, nth=): exact rank selection by an MSB-first descent whose
-// branch at each bit is global (bitmap_kernels.hip bsi_kth_*).  One step of
+// branch at each bit is global (bsi_kernels.hip bsi_kth_*).  One step of
 // the chain, shared by the step kernel (every wave replays the bits already
 // decided) and the host (the final replay): the current candidate set holds
 // ``tot`` values of which ``c1`` have the bit set, ``r`` is the 0-based rank

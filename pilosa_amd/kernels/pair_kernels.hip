@@ -122,6 +122,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
+#include "device_util.h"
 
 namespace pk {
 namespace {
@@ -132,56 +133,6 @@ constexpr uint32_t NONE = 0xffffffffu;
 // Container indices stay below it (the engine takes the pair path only for
 // views of fewer than 0xffffffff containers).
 constexpr uint32_t PRECOUNTED = 0xfffffffeu;
-
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
-// Wave-wide sum through DPP row ops (ockl), not __shfl_xor: the latter is six
-// dependent ds_bpermute round trips through the LDS pipe per call.
-extern "C" __device__ int __ockl_wfred_add_i32(int);
-__device__ __forceinline__ int wave_sum(int v) { return __ockl_wfred_add_i32(v); }
-
-__device__ __forceinline__ uint32_t xcd_remap_blocks(uint32_t bid, uint32_t nblk) {
-  const uint32_t nx = 8;
-  const uint32_t xcd = bid % nx, loc = bid / nx;
-  const uint32_t q = nblk / nx, r = nblk % nx;
-  const uint32_t base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + loc;
-}
-
-// Payload/meta pointers live in ViewDev as generic pointers; casting them to
-// the global address space gives global_load (vmcnt only) instead of
-// flat_load, which also counts against lgkmcnt and so serialises with LDS.
-// (The host compilation pass parses these bodies too, without address spaces.)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define PK_GLOBAL __attribute__((address_space(1)))
-#else
-#define PK_GLOBAL
-#endif
-template <class T>
-__device__ __forceinline__ const PK_GLOBAL T* gp(const T* p) {
-  return (const PK_GLOBAL T*)(p);
-}
-
-__device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// Key-presence mask and absolute first-container index of dense row d in shard s.
-__device__ __forceinline__ uint32_t row_keys(const ViewDev& v, int s, int64_t d, int64_t& lo) {
-  lo = 0;
-  if (d < 0) return 0;
-  const auto rp = gp(v.rowptr + int64_t(s) * (v.D + 1));
-  const uint32_t r0 = rp[d];
-  lo = gp(v.shard_base)[s] + r0;
-  // the view's mask table: one 2-byte load instead of the row's metas
-  if (v.keymask) return gp(v.keymask)[int64_t(s) * v.D + d];
-  const uint32_t r1 = rp[d + 1];
-  const int n = int(r1 - r0);
-  if (n == 16) return 0xffffu;
-  uint32_t pres = 0;
-#pragma unroll
-  for (int k = 0; k < 16; k++)
-    if (k < n) pres |= 1u << meta_j(gp(v.meta)[lo + k]);
-  return pres;
-}
 
 // keymask[s][d] = row_keys() of every (shard, dense row): built once per view
 // generation (DeviceView.ensure_keymask), it turns pair_build's up-to-16
@@ -239,13 +190,9 @@ __global__ __launch_bounds__(256) void pair_build_kernel(const QueryProg* __rest
 
 // ---- container primitives (wave-cooperative, lb = wave-private 1024-word LDS bitmap)
 
-__device__ __forceinline__ const uint16_t* payload_of(const ViewDev& v, int64_t m) {
-  return v.payload + meta_off16(m) * 8;
-}
-
 __device__ __forceinline__ void lds_clear(uint64_t* lb) {
   ulong2* l2 = reinterpret_cast<ulong2*>(lb);
-  const int lane = lane_id();
+  const int lane = wave_lane();
 #pragma unroll
   for (int i = 0; i < 8; i++) l2[i * 64 + lane] = make_ulong2(0, 0);
 }
@@ -257,7 +204,7 @@ __device__ __forceinline__ void lds_clear(uint64_t* lb) {
 // was ~60 % of a 32-query batch's pair-kernel time (profiles/r05_serve/).
 template <bool BST = false>
 __device__ __forceinline__ void stage(uint64_t* lb, const uint16_t* p, int64_t m) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const int type = meta_type(m);
   ulong2* l2 = reinterpret_cast<ulong2*>(lb);
   if (type == CT_BITMAP) {
@@ -267,7 +214,7 @@ __device__ __forceinline__ void stage(uint64_t* lb, const uint16_t* p, int64_t m
     for (int i = 0; i < 8; i++) t[i] = g[i * 64 + lane];
 #pragma unroll
     for (int i = 0; i < 8; i++) l2[i * 64 + lane] = t[i];
-    lds_wait();
+    lds_fence();
     return;
   }
   uint32_t* l32 = reinterpret_cast<uint32_t*>(lb);
@@ -286,7 +233,7 @@ __device__ __forceinline__ void stage(uint64_t* lb, const uint16_t* p, int64_t m
       }
       if (!cleared) {   // the clear overlaps the first round of loads
         lds_clear(lb);
-        lds_wait();
+        lds_fence();
         cleared = true;
       }
 #pragma unroll
@@ -305,11 +252,11 @@ __device__ __forceinline__ void stage(uint64_t* lb, const uint16_t* p, int64_t m
     if (!cleared) {
       lds_clear(lb);
     }
-    lds_wait();
+    lds_fence();
     return;
   }
   lds_clear(lb);
-  lds_wait();
+  lds_fence();
   if (type == CT_ARRAY) {
     const int n = meta_n(m);
     const auto p4 = gp(reinterpret_cast<const uint4*>(p));
@@ -342,7 +289,7 @@ __device__ __forceinline__ void stage(uint64_t* lb, const uint16_t* p, int64_t m
       }
     }
   }
-  lds_wait();
+  lds_fence();
 }
 
 // Dword of value v's bit in a 1024-word bitmap (the staged one in LDS, or a
@@ -379,7 +326,7 @@ __device__ __forceinline__ int probe8(BM bm, const uint4 v4) {
 // so the wave sum subtracts it once).
 template <class BM>
 __device__ __forceinline__ int pad_hits(BM bm, int slots, int n) {
-  return lane_id() == 0 ? int(bm[0] & 1u) * (slots - n) : 0;
+  return wave_lane() == 0 ? int(bm[0] & 1u) * (slots - n) : 0;
 }
 
 // Whole-array probe with the next chunk's load issued before the current
@@ -387,7 +334,7 @@ __device__ __forceinline__ int pad_hits(BM bm, int slots, int n) {
 // chunks; every lane probes 8 slots per iteration.
 template <class BM>
 __device__ __forceinline__ int probe_pipe(BM bm, const uint16_t* arr, int n) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const auto p4 = gp(reinterpret_cast<const uint4*>(arr));
   const int n8 = (n + 7) >> 3;
   const int iters = (n8 + 63) >> 6;
@@ -409,7 +356,7 @@ __device__ __forceinline__ int probe_pipe(BM bm, const uint16_t* arr, int n) {
 
 // |staged ∩ B| for a bitmap B in global memory 
 __device__ __forceinline__ int and_lds_bitmap(const uint64_t* lb, const uint64_t* y) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const ulong2* a = reinterpret_cast<const ulong2*>(lb);
   const auto b = gp(reinterpret_cast<const ulong2*>(y));
   int c = 0;
@@ -428,7 +375,7 @@ __device__ __forceinline__ int and_lds_bitmap(const uint64_t* lb, const uint64_t
 
 // |A ∩ B| of two bitmaps in global memory
 __device__ __forceinline__ int and_global_bitmaps(const uint64_t* x, const uint64_t* y) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const auto a = gp(reinterpret_cast<const ulong2*>(x));
   const auto b = gp(reinterpret_cast<const ulong2*>(y));
   int c = 0;
@@ -447,7 +394,7 @@ __device__ __forceinline__ int and_global_bitmaps(const uint64_t* x, const uint6
 
 // Count bits of a run container inside the staged bitmap.
 __device__ __forceinline__ int runs_in_lds(const uint64_t* lb, const uint16_t* p) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const auto pr = gp(p);
   const int nr = pr[0];
   int c = 0;
@@ -474,7 +421,7 @@ static_assert(SMALL_ARRAY_N % 64 == 0 && SMALL_ARRAY_N > 0, "SMALL_ARRAY_N must 
 constexpr int SMALL_ITERS = SMALL_ARRAY_N / 64;
 template <class BM>
 __device__ __forceinline__ int probe_small(BM bm, const uint16_t* arr, int n) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const auto p = gp(arr);
   if (n <= 64) {  // one value per lane, one probe (wave-uniform branch)
     const uint32_t v = lane < n ? uint32_t(p[lane]) : 0u;
@@ -504,13 +451,6 @@ __device__ __forceinline__ int count_vs_lds(const uint64_t* lb, const uint16_t* 
   return runs_in_lds(lb, p);
 }
 
-__device__ __forceinline__ uint64_t rl_u64(uint64_t v, int i) {
-  return (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(v >> 32), i))) << 32) |
-         uint32_t(__builtin_amdgcn_readlane(int(v), i));
-}
-
-__device__ __forceinline__ int64_t rl64(int64_t v, int i) { return int64_t(rl_u64(uint64_t(v), i)); }
-
 __device__ __forceinline__ int popc_and4(const uint4 a, const uint4 b) {
   return __popc(a.x & b.x) + __popc(a.y & b.y) + __popc(a.z & b.z) + __popc(a.w & b.w);
 }
@@ -526,7 +466,7 @@ __device__ __forceinline__ int popc_and4(const uint4 a, const uint4 b) {
 // for anything loaded later also covers the prefetch, which by then has had
 // the previous pair's work to arrive.
 __device__ __forceinline__ uint4 load_bhead(const uint16_t* p, int64_t m) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const int t = meta_type(m);
   if (t == CT_ARRAY && meta_n(m) <= 64) {
     const uint32_t v = uint32_t(gp(p)[min(lane, meta_n(m) - 1)]);
@@ -538,7 +478,7 @@ __device__ __forceinline__ uint4 load_bhead(const uint16_t* p, int64_t m) {
 
 // |B & staged| with B's head (load_bhead) already in registers
 __device__ __forceinline__ int count_vs_head(const uint64_t* lb, const uint16_t* p, int64_t m, const uint4 head) {
-  const int lane = lane_id();
+  const int lane = wave_lane();
   const int t = meta_type(m);
   const uint32_t* bm = reinterpret_cast<const uint32_t*>(lb);
   if (t == CT_ARRAY) {
@@ -607,7 +547,7 @@ __global__ __launch_bounds__(64) void twin_build_kernel(ViewDev v, int S, const 
   const int64_t rs = w >> 4;
   const int s = int(rs % S);
   const int r = int(rs / S);
-  const int lane = lane_id();
+  const int lane = wave_lane();
   ulong2* dst = reinterpret_cast<ulong2*>(twin + w * 1024);
   const int64_t d = rows[r];
   int64_t c = -1;
@@ -657,8 +597,8 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
                                                              const uint2* __restrict__ pairs,
                                                              int32_t* __restrict__ partial) {
   __shared__ uint64_t lb[1024];
-  const int lane = lane_id();
-  const int64_t gw = int64_t(xcd_remap_blocks(blockIdx.x, gridDim.x));
+  const int lane = wave_lane();
+  const int64_t gw = int64_t(xcd_remap(blockIdx.x, gridDim.x));
   const int nch = (Q + CQ - 1) / CQ;
   const int64_t u = gw / nch;
   if (u >= int64_t(S) * 16) return;
@@ -693,17 +633,17 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
     int i = __builtin_ctzll(todo);
     todo &= todo - 1;
     // head of pair i's B; inside the loop, of the pair after the current one
-    uint4 pf = load_bhead(reinterpret_cast<const uint16_t*>(rl_u64(pbl, i)), rl64(mb, i));
+    uint4 pf = load_bhead(reinterpret_cast<const uint16_t*>(rl_u64(pbl, i)), rl_i64(mb, i));
     for (;;) {
       const uint32_t a = __builtin_amdgcn_readlane(ea, i);
       const int va = __builtin_amdgcn_readlane(vai, i);
-      const int64_t mA = rl64(ma, i), mB = rl64(mb, i);
+      const int64_t mA = rl_i64(ma, i), mB = rl_i64(mb, i);
       const uint16_t* pA = reinterpret_cast<const uint16_t*>(rl_u64(pal, i));
       const uint16_t* pB = reinterpret_cast<const uint16_t*>(rl_u64(pbl, i));
       const int tA = meta_type(mA), tB = meta_type(mB);
       const int j = todo ? __builtin_ctzll(todo) : -1;
       const uint4 head = pf;
-      if (j >= 0) pf = load_bhead(reinterpret_cast<const uint16_t*>(rl_u64(pbl, j)), rl64(mb, j));
+      if (j >= 0) pf = load_bhead(reinterpret_cast<const uint16_t*>(rl_u64(pbl, j)), rl_i64(mb, j));
       int c = 0;
       if (a == cached && va == cached_v) {
         c = count_vs_head(lb, pB, mB, head);
@@ -715,13 +655,13 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
         } else if (!next_same && tA == CT_ARRAY && tB == CT_BITMAP && meta_n(mA) <= SMALL_ARRAY_N) {
           c = probe_small(gp(reinterpret_cast<const uint32_t*>(pB)), pA, meta_n(mA));
         } else if (!next_same && tA == CT_ARRAY && tB == CT_BITMAP) {
-          lds_wait();
+          lds_fence();
           stage<BST>(lb, pB, mB);
           cached = NONE;
           cached_v = -1;
           c = count_vs_lds(lb, pA, mA);
         } else {
-          lds_wait();  // previous readers of lb are done before it is rewritten
+          lds_fence();  // previous readers of lb are done before it is rewritten
           stage<BST>(lb, pA, mA);
           cached = a;
           cached_v = va;

@@ -23,8 +23,7 @@
 #include <stdint.h>
 
 #include "kernels.h"
-
-extern "C" __device__ long __ockl_wfred_add_i64(long);
+#include "device_util.h"
 
 namespace pk {
 
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void shift_dense_kernel(const uint64_t* __rest
     dst[w] = r;
     c += __popcll(r);
   }
-  const int64_t tot = int64_t(__ockl_wfred_add_i64(long(c)));
+  const int64_t tot = wave_sum_i64(c);
   if (lane == 0) {
     const int64_t key = int64_t(s) * 16 + k;
     (half ? spill_meta : main_meta)[key] =

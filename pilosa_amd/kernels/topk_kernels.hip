@@ -45,59 +45,13 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "device_util.h"
 
 namespace pk {
 namespace {
 
 constexpr int RFC_THREADS = 256;
 constexpr int RFC_OWNED_N = 32;   // arrays up to this size are counted by one lane
-
-extern "C" __device__ int __ockl_wfred_add_i32(int);
-
-__device__ __forceinline__ uint32_t rfc_xcd_remap(uint32_t bid, uint32_t nblk) {
-  // bijective: blocks b, b + 8, ... (one XCD) get consecutive units
-  const uint32_t nx = 8;
-  const uint32_t xcd = bid % nx, loc = bid / nx;
-  const uint32_t q = nblk / nx, r = nblk % nx;
-  const uint32_t base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + loc;
-}
-
-// global_load instead of flat_load (which also counts against lgkmcnt and so
-// serialises with the LDS reads of the counting loops)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define RFC_GLOBAL __attribute__((address_space(1)))
-#else
-#define RFC_GLOBAL
-#endif
-template <class T>
-__device__ __forceinline__ const RFC_GLOBAL T* gp(const T* p) {
-  return (const RFC_GLOBAL T*)(p);
-}
-
-// Absolute meta index of dense row d's key-j container in shard s, -1 = none.
-__device__ __forceinline__ int64_t find_container(const ViewDev& v, int s, int64_t d, int j) {
-  const auto rp = gp(v.rowptr + int64_t(s) * (v.D + 1));
-  const uint32_t r0 = rp[d];
-  const int64_t lo = gp(v.shard_base)[s] + r0;
-  if (v.keymask) {
-    const uint32_t pres = gp(v.keymask)[int64_t(s) * v.D + d];
-    return ((pres >> j) & 1) ? lo + __popc(pres & ((1u << j) - 1)) : -1;
-  }
-  const int n = min(int(rp[d + 1] - r0), 16);
-  for (int k = 0; k < n; k++) {
-    const int jj = meta_j(gp(v.meta)[lo + k]);
-    if (jj == j) return lo + k;
-    if (jj > j) break;   // a row's containers are sorted by key
-  }
-  return -1;
-}
-
-// the eight u16 values of one 16-byte payload load
-__device__ __forceinline__ uint32_t val8(const uint4& q, int k) {
-  const uint32_t w = k < 2 ? q.x : (k < 4 ? q.y : (k < 6 ? q.z : q.w));
-  return (w >> ((k & 1) * 16)) & 0xffff;
-}
 
 // bits of the staged filter inside [a, b] (a <= b < 65536)
 __device__ __forceinline__ int popc_range(const uint64_t* fb, uint32_t a, uint32_t b) {
@@ -115,7 +69,7 @@ __global__ __launch_bounds__(RFC_THREADS) void row_filter_counts_kernel(ViewDev 
                                                                         int rows_per_wave,
                                                                         unsigned long long* __restrict__ out) {
   __shared__ uint64_t fb[1024];   // the filter's (s, j) container as a bitmap
-  const uint32_t unit = rfc_xcd_remap(blockIdx.x, gridDim.x);
+  const uint32_t unit = xcd_remap(blockIdx.x, gridDim.x);
   const int chunk = int(unit % uint32_t(nchunk));
   const uint32_t sj = unit / uint32_t(nchunk);
   const int j = int(sj & 15), s = int(sj >> 4);
@@ -128,7 +82,7 @@ __global__ __launch_bounds__(RFC_THREADS) void row_filter_counts_kernel(ViewDev 
   const int64_t xm = gp(xv.meta)[xc];
   if (meta_n(xm) == 0) return;
   const int xt = meta_type(xm);
-  const uint16_t* xp = xv.payload + meta_off16(xm) * 8;
+  const uint16_t* xp = payload_of(xv, xm);
   {
     ulong2* l2 = reinterpret_cast<ulong2*>(fb);
     if (xt == CT_BITMAP) {
@@ -188,7 +142,7 @@ __global__ __launch_bounds__(RFC_THREADS) void row_filter_counts_kernel(ViewDev 
     const bool live = n > 0 && (t == CT_ARRAY || t == CT_BITMAP || t == CT_RUN);
     const bool owned = live && t == CT_ARRAY && n <= RFC_OWNED_N;
     if (owned) {
-      const auto p4 = gp(reinterpret_cast<const uint4*>(fv.payload + meta_off16(m) * 8));
+      const auto p4 = gp(reinterpret_cast<const uint4*>(payload_of(fv, m)));
       int cnt = 0;
       for (int e = 0; e < ((n + 7) >> 3); e++) {
         const uint4 q = p4[e];
@@ -204,9 +158,8 @@ __global__ __launch_bounds__(RFC_THREADS) void row_filter_counts_kernel(ViewDev 
     while (coop) {
       const int src = __builtin_ctzll(coop);
       coop &= coop - 1;
-      const int64_t cm = int64_t((uint64_t(uint32_t(__builtin_amdgcn_readlane(int(uint64_t(m) >> 32), src))) << 32) |
-                                 uint32_t(__builtin_amdgcn_readlane(int(m), src)));
-      const uint16_t* p = fv.payload + meta_off16(cm) * 8;
+      const int64_t cm = rl_i64(m, src);
+      const uint16_t* p = payload_of(fv, cm);
       const int ct = meta_type(cm);
       int cnt = 0;
       if (ct == CT_BITMAP) {
@@ -238,7 +191,7 @@ __global__ __launch_bounds__(RFC_THREADS) void row_filter_counts_kernel(ViewDev 
           if (b >= a) cnt += popc_range(fb, a, b);
         }
       }
-      const int total = __ockl_wfred_add_i32(cnt);
+      const int total = wave_sum(cnt);
       if (lane == 0 && total) atomicAdd(out + db + src, (unsigned long long)total);
     }
   }

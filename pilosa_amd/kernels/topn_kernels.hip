@@ -36,6 +36,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "device_util.h"
 
 // Cost-isolation bits of the src-TopN kernels (PILOSA_TOPN_DBG): read only
 // in the kbench module (pilosa_amd/native/build.py --kbench); the shipped
@@ -53,26 +54,6 @@ constexpr int TN_THREADS = 1024;
 constexpr int TN_WAVES = TN_THREADS / 64;
 constexpr int64_t SW = int64_t(1) << 20;  // columns per shard
 constexpr int64_t CP_STRIDE = SW + 1;      // colptr entries per shard
-
-__device__ __forceinline__ uint32_t tn_xcd_remap(uint32_t bid, uint32_t nblk) {
-  // consecutive units (same shard, different queries) land on one XCD so the
-  // shard's colptr / slot lists are shared through that XCD's L2
-  const uint32_t nx = 8;
-  const uint32_t xcd = bid % nx, loc = bid / nx;
-  const uint32_t q = nblk / nx, r = nblk % nx;
-  const uint32_t base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + loc;
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-#define TN_GLOBAL __attribute__((address_space(1)))
-#else
-#define TN_GLOBAL
-#endif
-template <class T>
-__device__ __forceinline__ const TN_GLOBAL T* gp(const T* ptr) {
-  return (const TN_GLOBAL T*)(ptr);
-}
 
 // f(x) for every value x of the container described by meta word m; the
 // threads tid, tid + nthr, ... of a group split the work.
@@ -287,7 +268,7 @@ template <int MODE>
 __global__ __launch_bounds__(TN_THREADS, 8) void topn_src_kernel(TopNLaunch p) {
   extern __shared__ uint32_t hist[];
   __shared__ BlockScratch bs;
-  const uint32_t unit = tn_xcd_remap(blockIdx.x, gridDim.x);
+  const uint32_t unit = xcd_remap(blockIdx.x, gridDim.x);
   const int q = int(unit % p.Q), s = int(unit / p.Q);
   const int tid = threadIdx.x;
   const int K = p.K;
@@ -516,7 +497,7 @@ __global__ __launch_bounds__(TN_THREADS, 8) void topn_src_kernel(TopNLaunch p) {
 // ids= re-count from the histograms phase 1 kept (hist_in): one 256-thread
 // block per (query, shard) gathers the slot counts of that query's ids.
 __global__ __launch_bounds__(256) void topn_gather_kernel(TopNLaunch p) {
-  const uint32_t unit = tn_xcd_remap(blockIdx.x, gridDim.x);
+  const uint32_t unit = xcd_remap(blockIdx.x, gridDim.x);
   const int q = int(unit % p.Q), s = int(unit / p.Q);
   const HistLayout L(p.K - p.R, p.H32, p.H16);
   const auto h = gp(p.hist_in + unit_hist_base(p, q, s, L.words));
@@ -681,7 +662,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
   extern __shared__ uint32_t tab[];
   __shared__ int grab[2];
   // one workgroup per (shard, key j[, half]); consecutive blocks share a shard (XCD L2)
-  const int unit = int(tn_xcd_remap(blockIdx.x, gridDim.x));
+  const int unit = int(xcd_remap(blockIdx.x, gridDim.x));
   constexpr int HB = NQ == 32 ? 1 : 0;  // half bit
   const int s = unit >> (4 + HB), j = (unit >> HB) & 15;
   const int lo = HB ? (unit & 1) * 32768 : 0;
@@ -718,7 +699,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
     for (uint32_t m = bmq; m; m &= m - 1) {
       const int q = __builtin_ctz(m);
       const int64_t kk = (int64_t(q) * p.S + s) * 16 + j;
-      const auto w32 = reinterpret_cast<const TN_GLOBAL uint32_t*>(gp(p.src_vals + p.src_offs[kk]));
+      const auto w32 = reinterpret_cast<const PK_GLOBAL uint32_t*>(gp(p.src_vals + p.src_offs[kk]));
       uint32_t v[PER];
 #pragma unroll
       for (int t = 0; t < PER; t++)
@@ -767,7 +748,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
         }
       }
     } else if (!((bmq >> q) & 1u) && !(PK_DBG(p) & 512)) {
-      const auto w = reinterpret_cast<const TN_GLOBAL uint64_t*>(vals);
+      const auto w = reinterpret_cast<const PK_GLOBAL uint64_t*>(vals);
       for (int i = lane + (lo >> 6); i < (lo + NLO) >> 6; i += 64)
         for (uint64_t bb = w[i]; bb; bb &= bb - 1) {
           const int x = i * 64 + __builtin_ctzll(bb);
@@ -802,11 +783,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
     const int64_t ml = cl >= 0 ? p.v.meta[sb + cl] : 0;
     uint64_t live = __ballot(cl >= 0);
     if (!live) continue;
-    auto row_meta = [&](int r) -> int64_t {
-      const uint32_t lo = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(ml)), r));
-      const uint32_t hi = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(uint64_t(ml) >> 32)), r));
-      return int64_t((uint64_t(hi) << 32) | lo);
-    };
+    auto row_meta = [&](int r) -> int64_t { return rl_i64(ml, r); };
     // lane l takes values base + 8l .. +7 with ONE 16-byte load (the payload
     // is 16-byte aligned and padded to 8 values).  16 values per lane per
     // step (two loads, 124 VGPRs) measured 10.7 vs 10.4 ms (profiles/r03_ch16)
@@ -816,7 +793,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
     // count the loads in flight instead of draining them all (vmcnt(0)).
     // m == 0 (no container to prefetch) reads the payload's first chunk.
     auto load_chunk = [&](int64_t m, int base, uint4& x, int& nv) {
-      const uint4* pp4 = reinterpret_cast<const uint4*>(p.v.payload + meta_off16(m) * 8);
+      const uint4* pp4 = reinterpret_cast<const uint4*>(payload_of(p.v, m));
       const int i0 = base + 8 * lane;
       const int n = meta_n(m);
       nv = min(max(n - i0, 0), 8);
@@ -879,7 +856,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
       }
       load_chunk(lr >= 0 && meta_type(lm) == CT_ARRAY ? lm : 0, lbase, ldb, ldv);
       adv();
-      const uint16_t* pp = p.v.payload + meta_off16(m) * 8;
+      const uint16_t* pp = payload_of(p.v, m);
       if (ty == CT_ARRAY && !(PK_DBG(p) & 64)) {
         // an array gives a lane at most 64 values (6-7 carry-save planes).
         // All 8 table reads issue before any is consumed (one LDS wait per
@@ -1050,7 +1027,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
     // a quad's first chunk loads with the quad before it
     auto first_chunk = [&](int c, int64_t m) -> uint4 {
       const int nn = c >= 0 ? meta_n(m) : 0;
-      return reinterpret_cast<const uint4*>(p.v.payload + meta_off16(m) * 8)[min(sl, max(nn - 1, 0) >> 3)];
+      return reinterpret_cast<const uint4*>(payload_of(p.v, m))[min(sl, max(nn - 1, 0) >> 3)];
     };
     uint4 px0 = first_chunk(cq, mq);
     // a quad's totals are added after the next quad's first round is counted
@@ -1070,7 +1047,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
       const int k = g4 + (lane >> 4);
       const int64_t m = mq;
       const int n = cq >= 0 ? meta_n(m) : 0;  // arrays only in this rank range
-      const uint4* pp = reinterpret_cast<const uint4*>(p.v.payload + meta_off16(m) * 8);
+      const uint4* pp = reinterpret_cast<const uint4*>(payload_of(p.v, m));
       const int lastc = max(n - 1, 0) >> 3;
       uint4 x0 = px0, x1;
       px0 = first_chunk(cq1, mq1);
@@ -1176,7 +1153,7 @@ __global__ __launch_bounds__(HOT_THREADS, 1) void topn_hot_kernel(TopNLaunch p) 
     while (B + 64 * g < R) {
       const int kl = B + 64 * g + lane;
       const int nl = cl >= 0 ? meta_n(ml) : 0;
-      const auto pp = gp(reinterpret_cast<const uint4*>(p.v.payload + meta_off16(ml) * 8));
+      const auto pp = gp(reinterpret_cast<const uint4*>(payload_of(p.v, ml)));
       // every lane loads (clamped to its row's last chunk; values past the
       // row are masked when counted), so no load sits behind a branch
       const int lastc = max(nl - 1, 0) >> 3;

@@ -5,7 +5,7 @@ Reference: fragment.go:1109-1141 (``sum``): per shard, for a filter F,
     count = |F & exists|
     sum   = sum_i 2^i (|F & exists & ~sign & bit_i| - |F & exists & sign & bit_i|)
 
-The per-filter kernel (bitmap_kernels.hip bsi_sum) streams every bit plane
+The per-filter kernel (bsi_kernels.hip bsi_sum_keys_kernel) streams every bit plane
 once per filter.  For a batch of Q filters the same numbers are one count
 matrix C = F x P^T over all 2^20 * S bit positions, where the rows of P are the
 filter-independent planes
@@ -158,7 +158,7 @@ def bsi_sum_matrix(engine: GpuEngine, filters: Sequence[Optional[object]], bv: D
 
 
 # ---------------------------------------------------------------- Percentile
-# The chain of the device descent (kernels.h kth_chain, bitmap_kernels.hip
+# The chain of the device descent (kernels.h kth_chain, bsi_kernels.hip
 # bsi_kth_step) in Python: the same rule, line for line, so it can be checked
 # against brute force without a device (tests/test_percentile.py).
 

@@ -5,7 +5,8 @@ a *container arena* (layout documented in pilosa_amd/native/pyroaring.cpp):
 CSR row directory per local shard + packed container metadata + payload pool.
 The HIP kernels in pilosa_amd/kernels/bitmap_kernels.hip evaluate a whole
 batch of boolean query programs over all local shards of the arena in one
-launch (reference per-shard worker loop: executor.go:2564-2611 — replaced).
+launch (reference per-shard worker loop: executor.go:2564-2611 — replaced);
+the BSI kernels on the same programs are in pilosa_amd/kernels/bsi_kernels.hip.
 
 Query programs are tiny postfix byte codes over <=16 leaves (a leaf = one row
 of one view).  ``Expr`` trees are compiled here.

@@ -7,7 +7,8 @@ device arenas of the involved field-views:
 
 * ``count``     Count(<bitmap tree>)                 -> expr_count
 * ``bitmap``    Row/Intersect/Union/Difference/Xor/Not/time ranges -> materialize
-* ``bsi_sum``   Sum(<filter>, field=f)                -> bsi_sum kernel
+* ``bsi_sum``   Sum(<filter>, field=f)                -> bsi_sum_keys (this and
+                the other bsi_* kernels: kernels/bsi_kernels.hip)
 * ``bsi_percentile`` Percentile(<filter>, field=f, nth=p) -> bsi_kth_init +
                 one bsi_kth_step launch per bit (global MSB-first descent)
 * ``topk``      TopK(<filter>, field=f, k=n)           -> row_filter_counts (one
@@ -2185,7 +2186,7 @@ def _fold_subshards_value(vals: np.ndarray, cnts: np.ndarray, is_min: bool, M: O
 
 def _minmax_per_shard(o: np.ndarray, which: str):
     """Per-shard (value, count) of the BSI min/max descents ``o`` int64[S, 16, 10]
-    (bitmap_kernels.hip bsi_minmax_kernel, per key: 0/1 max |neg| + count,
+    (bsi_kernels.hip bsi_minmax_kernel, per key: 0/1 max |neg| + count,
     2/3 min pos, 4/5 max pos, 6/7 min |neg|, 8/9 any pos / any neg), vectorised
     over the shards with fragment.min/max's sign rules (fragment.go:1145-1225);
     count 0 = no value in the shard."""

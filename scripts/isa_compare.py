@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 code of one .hip file between two revisions, kernel by kernel.
+"""Compare the gfx950 code of .hip files between two revisions, kernel by kernel.
 
   python scripts/isa_compare.py REV_A REV_B pilosa_amd/kernels/pair_kernels.hip
+  python scripts/isa_compare.py REV_A REV_B PATHS_A [PATHS_B]
 
-REV is anything `git archive` takes, or `.` for the working tree.  Each side's
-kernel directory (so its own kernels.h) goes to a temp directory and is
-cross-compiled to assembly; no GPU is needed.  Per kernel the report says
+REV is anything `git archive` takes, or `.` for the working tree.  PATHS is a
+comma-separated list of files whose kernels are pooled on that side (PATHS_B
+defaults to PATHS_A); a file a revision does not have is skipped with a note.
+So kernels can be followed across a file split:
+
+  python scripts/isa_compare.py HEAD~1 . pilosa_amd/kernels/bitmap_kernels.hip,pilosa_amd/kernels/bsi_kernels.hip
+
+Each side's kernel directory (so its own headers) goes to a temp directory and
+is cross-compiled to assembly; no GPU is needed.  Per kernel the report says
 whether the normalised text (comments stripped, .LBB labels renumbered) is
 identical, and gives VGPRs / SGPRs / LDS / scratch before -> after, the
 instruction count and the opcode-count delta.  Kernels are matched by their
@@ -28,16 +35,25 @@ RENAMED = {"shadow_build_kernel": "twin_build_kernel"}
 STATS = (("vgpr", "NumVgprs"), ("sgpr", "TotalNumSgprs"), ("lds", "LDSByteSize"), ("scratch", "ScratchSize"))
 
 
-def assembly(rev, path, tmp):
-    src = os.path.dirname(path) or "."
-    if rev != ".":
-        src = os.path.join(tmp, "src")
-        os.makedirs(src)
-        tar = subprocess.run(["git", "archive", rev, "--", os.path.dirname(path)], check=True, capture_output=True)
-        subprocess.run(["tar", "-x", "--strip-components", str(path.count("/")), "-C", src], input=tar.stdout, check=True)
-    out = os.path.join(tmp, "out.s")
-    subprocess.run([HIPCC, *FLAGS, os.path.join(src, os.path.basename(path)), "-o", out], check=True)
-    return open(out).read()
+def assembly(rev, paths, tmp):
+    """{path: assembly} of the listed files at rev; a file the revision does not have is skipped"""
+    out = {}
+    for n, path in enumerate(paths):
+        src = os.path.dirname(path) or "."
+        if rev != ".":
+            src = os.path.join(tmp, "src%d" % n)
+            os.makedirs(src)
+            tar = subprocess.run(["git", "archive", rev, "--", os.path.dirname(path)], check=True, capture_output=True)
+            subprocess.run(["tar", "-x", "--strip-components", str(path.count("/")), "-C", src], input=tar.stdout,
+                           check=True)
+        file = os.path.join(src, os.path.basename(path))
+        if not os.path.exists(file):
+            print("note: %s does not exist at %s, skipped" % (path, rev))
+            continue
+        asm = os.path.join(tmp, "out%d.s" % n)
+        subprocess.run([HIPCC, *FLAGS, file, "-o", asm], check=True)
+        out[path] = open(asm).read()
+    return out
 
 
 def key_of(mangled):
@@ -73,11 +89,23 @@ def opcodes(lines):
     return collections.Counter(ln.split()[0] for ln in lines if not ln.endswith(":"))
 
 
+def pooled(rev, paths, tmp):
+    out = {}
+    for path, asm in assembly(rev, paths, tmp).items():
+        for key, val in kernels(asm).items():
+            if key in out:
+                sys.exit("%s: kernel %s is in more than one of %s" % (rev, key, ", ".join(paths)))
+            out[key] = val
+    return out
+
+
 def main():
-    rev_a, rev_b, path = sys.argv[1:4]
+    rev_a, rev_b = sys.argv[1:3]
+    paths_a = sys.argv[3].split(",")
+    paths_b = sys.argv[4].split(",") if len(sys.argv) > 4 else paths_a
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        a, b = kernels(assembly(rev_a, path, ta)), kernels(assembly(rev_b, path, tb))
-    print("%s: %s -> %s (%s)" % (path, rev_a, rev_b, " ".join(FLAGS)))
+        a, b = pooled(rev_a, paths_a, ta), pooled(rev_b, paths_b, tb)
+    print("%s @ %s -> %s @ %s (%s)" % (",".join(paths_a), rev_a, ",".join(paths_b), rev_b, " ".join(FLAGS)))
     same = 0
     for key in sorted(set(a) | set(b)):
         if key not in a or key not in b:
@@ -92,7 +120,9 @@ def main():
         delta = {op: ob[op] - oa[op] for op in sorted(set(oa) | set(ob)) if ob[op] != oa[op]}
         if delta:
             print("    opcode delta: " + ", ".join("%s %+d" % kv for kv in delta.items()))
-    print("%d of %d kernels identical" % (same, len(set(a) | set(b))))
+    both = len(set(a) & set(b))
+    print("%d of %d kernels identical, %d different, %d on one side only" % (
+        same, len(set(a) | set(b)), both - same, len(set(a) ^ set(b))))
 
 
 if __name__ == "__main__":
