@@ -23,6 +23,8 @@ import threading
 from fractions import Fraction
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
+
 from pilosa_amd import _roaring
 from pilosa_amd.errors import (BadRequestError, ErrBSIGroupNotFound, ErrFieldNotFound, ErrIndexNotFound,
                                ErrIndexRequired, ErrTooManyWrites, PilosaError, wrap)
@@ -45,6 +47,9 @@ MAX_INT = (1 << 63) - 1
 # where it applies; PILOSA_PERCENTILE_DEVICE=0 keeps every call on the generic
 # path (measurements: profiles/percentile/README.md)
 _PERCENTILE_DEVICE_DEFAULT = "1"
+# Distinct(): the device pass (GpuExecutor.bsi_distinct) against the host gather;
+# the default follows the measurement in profiles/distinct/README.md
+_DISTINCT_DEVICE_DEFAULT = "1"
 
 
 # a request that is one unfiltered BSI aggregate: Sum|Min|Max(field=<name>)
@@ -61,6 +66,10 @@ def _topk_device() -> str:
     """PILOSA_TOPK_DEVICE: "0" keeps TopK() on the host, "programs" / "kernel"
     force one device route, anything else lets GpuExecutor.topk choose."""
     return os.environ.get("PILOSA_TOPK_DEVICE", "")
+
+
+def _distinct_device() -> bool:
+    return os.environ.get("PILOSA_DISTINCT_DEVICE", _DISTINCT_DEVICE_DEFAULT) not in ("0", "")
 
 
 def _percentile_device() -> bool:
@@ -115,6 +124,40 @@ class ValCount:
 
     def __repr__(self):
         return f"ValCount({self.val}, {self.count})"
+
+
+class SignedRow:
+    """Distinct()'s result: a set of signed integers as two Rows, ``pos``
+    holding every value v >= 0 as column id v and ``neg`` holding |v| for every
+    v < 0.  The ids are values, not columns: they are never key-translated and
+    carry no attributes (which is why this is not a Row)."""
+    __slots__ = ("pos", "neg")
+
+    def __init__(self, pos: Optional[Row] = None, neg: Optional[Row] = None):
+        self.pos = pos if pos is not None else Row()
+        self.neg = neg if neg is not None else Row()
+
+    @classmethod
+    def from_values(cls, values) -> "SignedRow":
+        """From real (base applied) int64 values, in any order, duplicates allowed."""
+        v = np.asarray(values, dtype=np.int64)
+        return cls(Row(np.unique(v[v >= 0]).astype(np.uint64)), Row(np.unique(-v[v < 0]).astype(np.uint64)))
+
+    def union(self, o: "SignedRow") -> "SignedRow":
+        return SignedRow(self.pos.union(o.pos), self.neg.union(o.neg))
+
+    def values(self) -> np.ndarray:
+        """Every value, ascending (int64)."""
+        return np.concatenate([-self.neg.columns().astype(np.int64)[::-1], self.pos.columns().astype(np.int64)])
+
+    def to_json(self):
+        return {"pos": self.pos.to_json(), "neg": self.neg.to_json()}
+
+    def __eq__(self, o):
+        return isinstance(o, SignedRow) and self.pos == o.pos and self.neg == o.neg
+
+    def __repr__(self):
+        return f"SignedRow(pos={self.pos!r}, neg={self.neg!r})"
 
 
 class RowIdentifiers:
@@ -732,6 +775,8 @@ class Executor:
                 return self._minmax(index, c, shards, opt, "max")
             if n == "Percentile":
                 return self._percentile(index, c, shards, opt)
+            if n == "Distinct":
+                return self._distinct(index, c, shards, opt)
             if n == "MinRow":
                 return self._minmax_row(index, c, shards, opt, True)
             if n == "MaxRow":
@@ -1438,6 +1483,57 @@ class Executor:
             return False
         mesh = self.mesh
         return mesh is None or mesh.world <= 1
+
+    def distinct_field(self, index: str, c: Call):
+        """Distinct()'s argument checks -> (field name, its BSI group)."""
+        for k in c.args:
+            if k != "field":
+                raise PilosaError(f'Distinct(): unknown argument "{k}"')
+        fname = c.args.get("field")
+        if not fname or not isinstance(fname, str):
+            raise PilosaError("Distinct(): field required")
+        if len(c.children) > 1:
+            raise PilosaError("Distinct() only accepts a single bitmap input")
+        f = self.holder.field(index, fname)
+        if f is None:
+            raise ErrFieldNotFound
+        b = f.bsi_group(fname)
+        if f.type != FIELD_TYPE_INT or b is None:
+            raise PilosaError(f'cannot compute Distinct() on non-integer field: "{fname}"')
+        return fname, b
+
+    def _distinct(self, index: str, c: Call, shards, opt) -> SignedRow:
+        """Distinct(field=<int field>) and Distinct(<one bitmap call>, field=):
+        the distinct values of a BSI int field (an extension: Pilosa v1.3 has
+        no such call).
+
+        The considered columns are those with a value in the field intersected
+        with the filter child (the ``exists & filter`` of Sum and Percentile).
+        The answer is a SignedRow: ``pos`` holds every distinct value v >= 0 as
+        column id v, ``neg`` holds |v| for every v < 0 -- real values, the
+        field's base applied -- once each over all shards.  No considered
+        column, a missing view or fragment, or an empty filter give an empty
+        SignedRow.
+
+        The map step returns the values of its shards (Fragment.distinct on the
+        host, one bsi_distinct_kernel pass over the local shards on the
+        device); the reduce step, between shards, nodes and ranks alike, is the
+        union of pos with pos and neg with neg."""
+        fname, b = self.distinct_field(index, c)
+
+        def map_fn(shard):
+            frag = self.holder.fragment(index, fname, VIEW_BSI_PREFIX + fname, shard)
+            if frag is None:
+                return SignedRow()
+            pos, neg = frag.distinct(self._bsi_filter_shard(index, c, shard), b.bit_depth)
+            # the base can turn a negative magnitude into a non-negative value and back
+            return SignedRow.from_values(np.concatenate([pos.astype(np.int64), -neg.astype(np.int64)]) + b.base)
+
+        local = (lambda ss: self.gpu.bsi_distinct(index, c, ss)) if self.gpu is not None and _distinct_device() \
+            else None
+        r = self.map_reduce(index, shards, c, opt, map_fn,
+                            lambda p, v: (p or SignedRow()).union(v or SignedRow()), local)
+        return r or SignedRow()
 
     def _minmax_row(self, index: str, c: Call, shards, opt, is_min: bool) -> Pair:
         fname = c.args.get("field")

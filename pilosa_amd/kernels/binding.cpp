@@ -308,6 +308,31 @@ std::tuple<int64_t, int64_t> bsi_kth_replay(torch::Tensor cnt1, int64_t depth, i
   return {int64_t(mag), int64_t(ut)};
 }
 
+// Distinct: mark the base-relative magnitudes of exists & filter in pos / neg (int64 words holding 2^depth
+// bits each, zeroed by the caller); returns the tile slots per workgroup used
+int64_t bsi_distinct(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor bsi_args, int64_t slots,
+                     int64_t mark, torch::Tensor pos, torch::Tensor neg) {
+  check_dev(progs, "progs");
+  check_dev(views, "views");
+  check_dev(pos, "pos");
+  check_dev(neg, "neg");
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24), "bsi_distinct: shard count");
+  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  const pk::BsiArgs b = bsi_args_from(bsi_args);
+  TORCH_CHECK(b.depth >= 0 && b.depth <= pk::DISTINCT_MAX_PLANES, "bsi_distinct: bit depth");
+  const int64_t words = std::max<int64_t>(1, (int64_t(1) << b.depth) >> 6);
+  for (const torch::Tensor* t : {&pos, &neg})
+    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->is_contiguous() && t->numel() >= words,
+                "pos / neg must be int64[max(1, 2^depth / 64)]");
+  const int n = pk::launch_bsi_distinct(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
+                                        reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+                                        int(slots), int(mark), reinterpret_cast<uint32_t*>(pos.data_ptr<int64_t>()),
+                                        reinterpret_cast<uint32_t*>(neg.data_ptr<int64_t>()), cur_stream(views));
+  TORCH_CHECK(n > 0, "bsi_distinct: not launched");
+  check_launch("bsi_distinct");
+  return n;
+}
+
 void bsi_minmax_fold(torch::Tensor o, int64_t F, int64_t G, int64_t is_min, torch::Tensor out) {
   check_dev(o, "o");
   check_dev(out, "out");
@@ -1171,6 +1196,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsi_kth_init", &bsi_kth_init, "Percentile: candidate tiles (exists & filter) and N, Nneg");
   m.def("bsi_kth_steps", &bsi_kth_steps, "Percentile: one descent launch per bit, MSB first");
   m.def("bsi_kth_replay", &bsi_kth_replay, "Percentile: host replay of the bit counts -> (magnitude, count)");
+  m.def("bsi_distinct", &bsi_distinct, "Distinct: mark the magnitudes of exists & filter in the pos / neg bitmaps");
+  m.def("distinct_slots", [](int64_t depth, int64_t want) { return int64_t(pk::distinct_slots(int(depth), int(want))); },
+        "Distinct: tile slots per workgroup the launcher uses for this depth and request");
   m.def("leaf_src", &leaf_src, "src containers of plain rows straight from the arena (TopN srcs)");
   m.def("row_counts", &row_counts, "row counts of (shard, dense row) entries (device rank caches)");
   m.def("topn_cache_counts", &topn_cache_counts, "cache-only TopN: [candidate x shard] row counts");

@@ -134,7 +134,21 @@ int launch_bsi_group_sum(const QueryProg* progs, int G, const ViewDev* views, in
                          int gchunk, int fmode, unsigned long long* out_sum, unsigned long long* out_cnt,
                          hipStream_t st);
 
-// TopK(field=, k=) (topk_kernels.hip, K25): out[d] += |row d ∩ filter| over
+// Distinct(field=) (distinct_kernels.hip, K26): bit v of pos / neg |= 1 for
+// every column of exists & filter (progs[0]; nprog == 0: no filter) holding the
+// base-relative value +v / -v; pos and neg hold 2^depth bits each (at least one
+// 32-bit word), zeroed by the caller.  depth <= DISTINCT_MAX_PLANES.  slots =
+// tile slots per workgroup (1, 2, 4 or 8; anything else: the largest that
+// fits), clamped by distinct_slots() to what the 160 KiB of LDS hold at this
+// depth.  mark: 0 always OR, 1 test the bit first, 2 also skip a repeat of the
+// thread's previous value.  Returns the slots used, -1 when nothing was launched
+// (depth out of range, grid too large).
+constexpr int DISTINCT_MAX_PLANES = 32;
+int distinct_slots(int depth, int want);
+int launch_bsi_distinct(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots, int mark,
+                        uint32_t* pos, uint32_t* neg, hipStream_t st);
+
+// TopK(field=, k=) (topk_kernels.hip, K25): out[d] +=|row d ∩ filter| over
 // the S arena shards for every dense row d of ``fv``; the filter is dense row
 // ``xd`` of ``*xv`` (same shard list), staged once per (shard, key) in LDS.
 // xv == nullptr: no filter, out[d] += |row d| from the metadata alone.

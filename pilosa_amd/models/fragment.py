@@ -770,6 +770,31 @@ class Fragment:
             return -v, c
         return self._max_unsigned(pos_, bit_depth)
 
+    def distinct(self, filt: Optional[Row], bit_depth: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The distinct base-relative values of ``exists & filt`` as two sorted
+        uint64 arrays of magnitudes: those of the non-negative and those of
+        the negative columns.  A per-column gather: every plane's columns
+        inside the considered set OR their bit into that column's magnitude,
+        so the cost is (considered columns) x bit_depth whatever the value
+        range is (a depth-40 field costs 40 passes, not 2^40 steps)."""
+        empty = np.zeros(0, np.uint64)
+        consider = self.row(BSI_EXISTS_BIT)
+        if filt is not None:
+            consider = consider.intersect(filt)
+        cols = consider.columns()
+        if len(cols) == 0:
+            return empty, empty
+        mags = np.zeros(len(cols), np.uint64)
+        for i in range(bit_depth):
+            on = self.row(BSI_OFFSET_BIT + i).intersect(consider).columns()
+            if len(on):
+                mags[np.searchsorted(cols, on)] |= np.uint64(1 << i)
+        neg = np.zeros(len(cols), bool)
+        on = self.row(BSI_SIGN_BIT).intersect(consider).columns()
+        if len(on):
+            neg[np.searchsorted(cols, on)] = True
+        return np.unique(mags[~neg]), np.unique(mags[neg])
+
     def _min_unsigned(self, filt: Row, bit_depth: int) -> Tuple[int, int]:
         mn, count = 0, 0
         for i in range(bit_depth - 1, -1, -1):

@@ -2037,6 +2037,47 @@ class GpuEngine:
         mag, count = self.ext.bsi_kth_replay(cnt1.contiguous(), depth, r, tot, largest)
         return (-int(mag) if largest else int(mag)), int(count)
 
+    # bit planes bsi_distinct_kernel transposes at most (kernels.h DISTINCT_MAX_PLANES)
+    DISTINCT_MAX_PLANES = 32
+
+    def bsi_distinct(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, slots: int = 0,
+                     mark: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+        """The distinct base-relative values of exists & filter as two sorted
+        uint64 arrays of magnitudes (non-negative, negative columns): one
+        bsi_distinct_kernel launch marks them in two device bitmaps of 2^depth
+        bits, then nonzero + gather on the device, so only the non-zero
+        (word index, word) pairs cross to the host, which expands them.
+
+        ``slots`` = tile slots per workgroup (0: the largest that fits the LDS
+        at this depth), ``mark`` = the marking variant (distinct_kernels.hip).
+
+        The two bitmaps are 2 * max(8, 2^depth / 8) bytes of device memory (2 x
+        8 MiB at depth 26) allocated and zeroed per request from torch's
+        caching allocator, outside the arenas' ``hbm_budget`` accounting;
+        concurrent requests hold a pair each until they return."""
+        torch = self.torch
+        empty = np.zeros(0, np.uint64)
+        S = bsi_view.S
+        if depth < 0 or depth > self.DISTINCT_MAX_PLANES:
+            raise NotImplementedError("bit depth beyond the transpose")
+        progs, ordered = self._bsi_filter_program(filt, bsi_view)
+        args = self.bsi_args(bsi_view, depth)
+        if not S or args[2] < 0:
+            return empty, empty
+        words = max(1, (1 << depth) >> 6)
+        bm = torch.zeros(2 * words, dtype=torch.int64, device=self.device)
+        tp, tv = self.upload_batch(progs, ordered)
+        self.ext.bsi_distinct(tp, tv, S, torch.from_numpy(args), int(slots), int(mark), bm[:words], bm[words:])
+        nz = torch.nonzero(bm).reshape(-1)
+        both = self.to_host(torch.stack([nz, bm[nz]])).numpy()
+        idx, w = both[0], both[1].view(np.uint64)
+        # bit b of word i of a bitmap is magnitude 64 * i + b
+        bits = np.unpackbits(w.view(np.uint8).reshape(-1, 8), axis=1, bitorder="little")
+        wi, b = np.nonzero(bits)
+        mags = (idx[wi].astype(np.uint64) % np.uint64(words)) * np.uint64(64) + b.astype(np.uint64)
+        neg = idx[wi] >= words
+        return mags[~neg], mags[neg]
+
     def _bsi_minmax_dev(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, which: str = ""):
         torch = self.torch
         S = bsi_view.S

@@ -11,6 +11,8 @@ device arenas of the involved field-views:
                 the other bsi_* kernels: kernels/bsi_kernels.hip)
 * ``bsi_percentile`` Percentile(<filter>, field=f, nth=p) -> bsi_kth_init +
                 one bsi_kth_step launch per bit (global MSB-first descent)
+* ``bsi_distinct`` Distinct(<filter>, field=f) -> bsi_distinct_kernel (one pass:
+                planes staged per (shard, key, slice), transposed, marked)
 * ``topk``      TopK(<filter>, field=f, k=n)           -> row_filter_counts (one
                 pass: filter staged per (shard, key), every row streamed past)
 * ``topn``      TopN phase-1/phase-2 with src          -> slot-index LDS
@@ -67,6 +69,36 @@ TOPK_DEFAULT_ROUTE = "kernel"
 # minimum spacing of device TopN index rebuilds per view (the reference
 # re-ranks its caches at most every 10 s too, cache.go:235-243)
 TOPN_INDEX_REBUILD_S = float(os.environ.get("PILOSA_TOPN_INDEX_REBUILD_S", "10"))
+
+
+def distinct_max_depth() -> int:
+    """PILOSA_DISTINCT_MAX_DEPTH: the deepest field Distinct() answers on the
+    device.  26 (two bitmaps of 8 MiB per request) is a memory choice, not a
+    measured optimum; 1..30 are accepted, anything else means the default."""
+    try:
+        v = int(os.environ.get("PILOSA_DISTINCT_MAX_DEPTH", "") or 26)
+    except ValueError:
+        return 26
+    return v if 1 <= v <= 30 else 26
+
+
+# tile slots per workgroup of bsi_distinct_kernel.  The largest that fits the
+# LDS was the starting point; measured on 64 shards at depth 20, one slot was
+# the fastest of 1, 2 and 4 in all three cases (0.22 / 0.59 / 0.31 ms against
+# 0.27 / 0.64 / 0.33 ms at 4: profiles/distinct/README.md) -- the small slab
+# lets two workgroups share a CU -- so 1 is the default
+DISTINCT_SLOTS_DEFAULT = 1
+
+
+def distinct_slots_env() -> int:
+    """PILOSA_DISTINCT_SLOTS: tile slots per workgroup of bsi_distinct_kernel
+    (1, 2, 4 or 8, clamped by the launcher to what fits the LDS at the field's
+    depth); anything else means DISTINCT_SLOTS_DEFAULT."""
+    try:
+        v = int(os.environ.get("PILOSA_DISTINCT_SLOTS", "") or DISTINCT_SLOTS_DEFAULT)
+    except ValueError:
+        return DISTINCT_SLOTS_DEFAULT
+    return v if v in (1, 2, 4, 8) else DISTINCT_SLOTS_DEFAULT
 
 
 class _Empty:
@@ -186,6 +218,7 @@ class GpuExecutor:
         self.group_sum_device = 0   # GroupBy(aggregate=Sum) calls answered by bsi_group_sum_kernel
         self.group_sum_per_filter = 0   # ... and by the per-filter kernel
         self.percentile_device = 0       # Percentile() calls answered by bsi_percentile (the fast path)
+        self.distinct_device = 0         # Distinct() map steps answered by bsi_distinct (K26)
         self.topk_device = 0             # TopK() map steps answered by row_filter_counts_kernel
         self.topk_programs = 0           # ... and by the per-row programs route
         # serving Count text path: host prep (parse..launch) vs result wait
@@ -407,7 +440,8 @@ class GpuExecutor:
                 "launches": self.launches, "rebuilds": self.rebuilds, "shardUpdates": self.shard_updates,
                 "rowUpdates": self.row_updates, "deviceWrites": self.device_writes,
                 "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
-                "percentileDevice": self.percentile_device, "groupSumDevice": self.group_sum_device,
+                "percentileDevice": self.percentile_device, "distinctDevice": self.distinct_device,
+                "groupSumDevice": self.group_sum_device,
                 "groupSumPerFilter": self.group_sum_per_filter, "topkDevice": self.topk_device,
                 "topkPrograms": self.topk_programs}
 
@@ -643,6 +677,42 @@ class GpuExecutor:
             return ValCount()
         self.launches += b.bit_depth
         return ValCount(r[0] + b.base, r[1])
+
+    def bsi_distinct(self, index: str, c: Call, shards: List[int]):
+        """Distinct(<filter>, field=) over the local shards -> ONE SignedRow of
+        real values: one bsi_distinct_kernel pass marks the base-relative
+        magnitudes of exists & filter in two device bitmaps
+        (GpuEngine.bsi_distinct); the base is applied here.
+        PILOSA_DISTINCT_MAX_DEPTH (default 26, accepted 1..30) bounds the
+        bitmaps (2 x 8 MiB at 26): a deeper field is left to the host.
+        PILOSA_DISTINCT_SLOTS sets the tile slots per workgroup (1, 2, 4, 8,
+        clamped to what fits the LDS at the field's depth; default
+        DISTINCT_SLOTS_DEFAULT)."""
+        from pilosa_amd.executor import SignedRow
+        fname = c.args.get("field")
+        f = self.holder.field(index, fname) if isinstance(fname, str) else None
+        if f is None or f.bsi_group(fname) is None or len(c.children) > 1:
+            raise NotImplementedError
+        b = f.bsi_group(fname)
+        if b.bit_depth > distinct_max_depth():
+            raise NotImplementedError
+        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
+        if bv is None:
+            self.distinct_device += 1   # no BSI view: answered here, without a launch
+            return SignedRow()
+        filt = None
+        if len(c.children) == 1:
+            filt = self.plan(index, c.children[0], shards)
+            if filt is EMPTY:
+                self.distinct_device += 1   # a filter known empty from the schema: no launch either
+                return SignedRow()
+        try:
+            pos, neg = self.engine.bsi_distinct(filt, bv, b.bit_depth, distinct_slots_env())
+        except CompileError:
+            raise NotImplementedError
+        self.distinct_device += 1
+        self.launches += 1
+        return SignedRow.from_values(np.concatenate([pos.astype(np.int64), -neg.astype(np.int64)]) + b.base)
 
     def hbm_bytes(self) -> int:
         with self.mu:

@@ -707,6 +707,9 @@ def decode(data: bytes):
 # group lists of GroupBy(aggregate=Sum): TAG_GROUPS' layout with k + 3 columns
 # per group (rows, count, sum, sum_count)
 TAG_GROUPS_SUM = 11
+# Distinct()'s SignedRow: [tag] then pos and neg one after the other, each as
+# TAG_ROW's body [segments, (shard, bytes) per segment, the segments' words]
+TAG_SIGNED_ROW = 12
 
 
 def encode_row_block(blk, device):
@@ -744,7 +747,7 @@ def _words_to_bytes(w: np.ndarray, n: int) -> bytes:
 
 def encode_partial(obj) -> np.ndarray:
     """One rank's partial result -> int64[...] (see the TAG_ layout)."""
-    from pilosa_amd.executor import GroupCount, RowIdentifiers, ValCount
+    from pilosa_amd.executor import GroupCount, RowIdentifiers, SignedRow, ValCount
     from pilosa_amd.models.cache import Pair, PairArray
     from pilosa_amd.models.row import Row
 
@@ -789,12 +792,17 @@ def encode_partial(obj) -> np.ndarray:
             return np.concatenate([np.array([TAG_GROUPS, len(obj), k, len(names)], np.int64), _bytes_to_words(names),
                                    mat.reshape(-1)])
         return msg()
-    if isinstance(obj, Row) and not obj.keys and not obj.attrs:
-        segs = [(int(s), bm.to_bytes()) for s, bm in sorted(obj.segments.items())]
-        head = [TAG_ROW, len(segs)]
+    def row_body(row):
+        segs = [(int(s), bm.to_bytes()) for s, bm in sorted(row.segments.items())]
+        head = [len(segs)]
         for s, b in segs:
             head += [s, len(b)]
-        return np.concatenate([np.array(head, np.int64)] + [_bytes_to_words(b) for _, b in segs])
+        return [np.array(head, np.int64)] + [_bytes_to_words(b) for _, b in segs]
+
+    if isinstance(obj, Row) and not obj.keys and not obj.attrs:
+        return np.concatenate([np.array([TAG_ROW], np.int64)] + row_body(obj))
+    if isinstance(obj, SignedRow):
+        return np.concatenate([np.array([TAG_SIGNED_ROW], np.int64)] + row_body(obj.pos) + row_body(obj.neg))
     if isinstance(obj, RowIdentifiers) and not obj.keys:
         a = np.asarray(obj.rows, dtype=np.uint64).view(np.int64) if obj.rows else np.zeros(0, np.int64)
         return np.concatenate([np.array([TAG_ROWIDS, -1 - len(obj.rows)], np.int64), a])
@@ -804,7 +812,7 @@ def encode_partial(obj) -> np.ndarray:
 def decode_partial(w: np.ndarray):
     """Inverse of :func:`encode_partial`."""
     from pilosa_amd import _roaring
-    from pilosa_amd.executor import FieldRow, GroupCount, RowIdentifiers, ValCount
+    from pilosa_amd.executor import FieldRow, GroupCount, RowIdentifiers, SignedRow, ValCount
     from pilosa_amd.models.cache import Pair
     from pilosa_amd.models.row import Row
 
@@ -866,16 +874,22 @@ def decode_partial(w: np.ndarray):
             out.append((GpuEngine.block_bitmaps(shards, c, offs, pay), shards))
         spill = out[1] if len(out) > 1 else ((), ())
         return row_from_bitmaps(out[0][0], out[0][1], *spill)
-    if tag == TAG_ROW:
-        ns = int(w[1])
-        hdr = w[2:2 + 2 * ns].reshape(ns, 2)
-        o = 2 + 2 * ns
+    def row_body(o):
+        ns = int(w[o])
+        hdr = w[o + 1:o + 1 + 2 * ns].reshape(ns, 2)
+        o += 1 + 2 * ns
         segs = {}
         for s, nb in hdr.tolist():
             nw = (nb + 7) // 8
             segs[int(s)] = _roaring.Bitmap.from_bytes(_words_to_bytes(w[o:o + nw], nb))
             o += nw
-        return Row(segments=segs)
+        return Row(segments=segs), o
+
+    if tag == TAG_ROW:
+        return row_body(1)[0]
+    if tag == TAG_SIGNED_ROW:
+        pos, o = row_body(1)
+        return SignedRow(pos, row_body(o)[0])
     raise ValueError(f"unknown partial tag {tag}")
 
 

@@ -4,13 +4,13 @@ from __future__ import annotations
 
 from typing import Any, List, Optional
 
-from pilosa_amd.executor import FieldRow, GroupCount, QueryResponse, RowIdentifiers, ValCount
+from pilosa_amd.executor import FieldRow, GroupCount, QueryResponse, RowIdentifiers, SignedRow, ValCount
 from pilosa_amd.models.cache import Pair, PairArray
 from pilosa_amd.models.row import Row
 from pilosa_amd.wire import (ATTR_TYPE_BOOL, ATTR_TYPE_FLOAT, ATTR_TYPE_INT, ATTR_TYPE_STRING,
                              QUERY_RESULT_TYPE_BOOL, QUERY_RESULT_TYPE_GROUPCOUNTS, QUERY_RESULT_TYPE_NIL,
                              QUERY_RESULT_TYPE_PAIR, QUERY_RESULT_TYPE_PAIRS, QUERY_RESULT_TYPE_ROW,
-                             QUERY_RESULT_TYPE_ROWIDENTIFIERS, QUERY_RESULT_TYPE_ROWIDS,
+                             QUERY_RESULT_TYPE_ROWIDENTIFIERS, QUERY_RESULT_TYPE_ROWIDS, QUERY_RESULT_TYPE_SIGNEDROW,
                              QUERY_RESULT_TYPE_UINT64, QUERY_RESULT_TYPE_VALCOUNT, pb)
 
 
@@ -21,7 +21,7 @@ def result_to_json(r: Any):
         return r
     if isinstance(r, int):
         return r
-    if isinstance(r, (Row, ValCount, Pair, RowIdentifiers, GroupCount, FieldRow, PairArray)):
+    if isinstance(r, (Row, ValCount, Pair, RowIdentifiers, GroupCount, FieldRow, PairArray, SignedRow)):
         return r.to_json()
     if isinstance(r, list):
         return [result_to_json(x) for x in r]
@@ -108,6 +108,10 @@ def result_to_pb(r: Any, call_name: str = ""):
     elif isinstance(r, ValCount):
         m.Type = QUERY_RESULT_TYPE_VALCOUNT
         m.ValCount.Val, m.ValCount.Count = r.val, r.count
+    elif isinstance(r, SignedRow):
+        m.Type = QUERY_RESULT_TYPE_SIGNEDROW
+        m.SignedRow.Neg.Columns.extend(int(c) for c in r.neg.columns())
+        m.SignedRow.Pos.Columns.extend(int(c) for c in r.pos.columns())
     elif isinstance(r, Pair):
         m.Type = QUERY_RESULT_TYPE_PAIR
         m.Pairs.add(ID=r.id, Key=r.key, Count=r.count)
@@ -158,6 +162,10 @@ def result_from_pb(m):
         return m.N
     if t == QUERY_RESULT_TYPE_VALCOUNT:
         return ValCount(m.ValCount.Val, m.ValCount.Count)
+    if t == QUERY_RESULT_TYPE_SIGNEDROW:
+        import numpy as np
+        return SignedRow(Row(np.array(list(m.SignedRow.Pos.Columns), dtype=np.uint64)),
+                         Row(np.array(list(m.SignedRow.Neg.Columns), dtype=np.uint64)))
     if t == QUERY_RESULT_TYPE_PAIR:
         p = m.Pairs[0]
         return Pair(p.ID, p.Count, p.Key)

@@ -88,6 +88,7 @@ QUERY_RESULT_TYPE_ROWIDS = 6
 QUERY_RESULT_TYPE_GROUPCOUNTS = 7
 QUERY_RESULT_TYPE_ROWIDENTIFIERS = 8
 QUERY_RESULT_TYPE_PAIR = 9
+QUERY_RESULT_TYPE_SIGNEDROW = 10   # pilosa_amd extension (Distinct)
 
 # Attr.Type codes
 ATTR_TYPE_STRING = 1
