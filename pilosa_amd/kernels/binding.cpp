@@ -424,6 +424,43 @@ void and2_count(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
   check_launch("and2_pairs");
 }
 
+// Count(Intersect) totals of a sorted KIND_AND2 part scattered into out, the
+// table-answered queries compacted out of the pair grid (launch_and2_total).
+void and2_count_total(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor ti, torch::Tensor out,
+                      torch::Tensor pairs, torch::Tensor partial, torch::Tensor work, int64_t cq, int64_t variant) {
+  check_dev(progs, "progs");
+  check_dev(views, "views");
+  check_dev(ti, "ti");
+  check_dev(out, "out");
+  check_dev(pairs, "pairs");
+  check_dev(partial, "partial");
+  check_dev(work, "work");
+  TORCH_CHECK(progs.numel() % int64_t(sizeof(pk::QueryProg)) == 0 &&
+                  reinterpret_cast<uintptr_t>(progs.data_ptr()) % 16 == 0,
+              "progs must hold whole programs, 16-byte aligned");
+  TORCH_CHECK(views.numel() % int64_t(sizeof(pk::ViewDev)) == 0, "views must hold whole ViewDev records");
+  const int64_t Q = progs.numel() / int64_t(sizeof(pk::QueryProg));
+  const int64_t V =views.numel() / int64_t(sizeof(pk::ViewDev));
+  TORCH_CHECK(Q < (int64_t(1) << 31) && S > 0 && S < (int64_t(1) << 27) && V > 0 && V < (int64_t(1) << 31),
+              "and2_count_total: batch size");
+  const int64_t n = Q * S * 16;
+  TORCH_CHECK(ti.scalar_type() == torch::kInt64 && ti.numel() == Q, "ti must be int64[Q]");
+  TORCH_CHECK(out.scalar_type() == torch::kInt64 && out.is_contiguous(), "out must be int64");
+  TORCH_CHECK(pairs.numel() * pairs.element_size() >= n * 8, "pairs scratch must hold S*16*Q uint2");
+  TORCH_CHECK(partial.scalar_type() == torch::kInt32 && partial.numel() >= n, "partial must be int32[S*16*Q]");
+  TORCH_CHECK(work.scalar_type() == torch::kUInt8 && work.is_contiguous() &&
+                  work.numel() >= pk::and2_work_bytes(Q) && reinterpret_cast<uintptr_t>(work.data_ptr()) % 256 == 0,
+              "work must be 256-byte aligned uint8[and2_work_bytes(Q)]");
+  const bool ok = pk::launch_and2_total(
+      reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), int(Q),
+      reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(V), int(S), ti.data_ptr<int64_t>(),
+      out.data_ptr<int64_t>(), out.numel(), reinterpret_cast<uint2*>(pairs.data_ptr()), partial.data_ptr<int32_t>(),
+      work.data_ptr<uint8_t>(), int(cq), int(variant), cur_stream(progs));
+  TORCH_CHECK(ok, "and2_count_total: no device-count pair kernel for ", Q, " queries, cq ", cq, ", variant ",
+              variant);
+  check_launch("and2_count_total");
+}
+
 pk::ViewDev viewdev_from(const torch::Tensor& vd);
 
 // Bitmap twins of dense array rows (DeviceView.ensure_twin).
@@ -1189,7 +1226,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("and2_count", &and2_count, "Count(Intersect(a,b)) batch via key-major pair kernels", py::arg("progs"),
         py::arg("views"), py::arg("S"), py::arg("pairs"), py::arg("partial"), py::arg("cq") = 0,
         py::arg("variant") = 1);
-  m.def("bsi_range", &bsi_range, "BSI predicate -> bitmap container per (shard, key)");
+  m.def("and2_count_total", &and2_count_total,
+        "Count(Intersect(a,b)) totals into out[ti]: table-answered queries compacted out of the pair grid");
+  m.def("and2_work_bytes", [](int64_t Q) { return pk::and2_work_bytes(Q); },
+        "bytes of and2_count_total's work scratch for Q queries");
+  m.def("bsi_range",&bsi_range, "BSI predicate -> bitmap container per (shard, key)");
   m.def("bsi_range_count", &bsi_range_count, "Count(Row(v <op> x)): fused BSI predicate + count");
   m.def("bsi_minmax", &bsi_minmax, "BSI min/max descents per (shard, key); which: 0 both, 1 Min, 2 Max",
         py::arg("progs"), py::arg("views"), py::arg("S"), py::arg("bsi_args"), py::arg("out"), py::arg("which") = 0);

@@ -83,6 +83,18 @@ void launch_partial_sum_scatter(const int32_t* partial, int64_t U, int n, const 
 // answered by pair_build from the table (shipped variants 6 / 39 / 63 only).
 void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int S, uint2* pairs, int32_t* partial,
                        int cq, int variant, hipStream_t st);
+// The same batch summed into out[ti[q]], with the queries a table answers in
+// every shard taken out of the pair grid on the device (pair_split_kernel).
+// progs: the sorted KIND_AND2 part, ti its submission indices, views[V].
+// work: and2_work_bytes(Q) bytes of 256-byte aligned scratch = counters
+// {live, table-answered} | live programs | table-answered list | live ti.
+// false = nothing launched: Q <= 128 or a variant / cq with no device-count
+// instantiation (built: variants 6 and 63 at 32 / 64 queries per wave).
+constexpr int64_t AND2_WORK_HEAD = 256;
+inline int64_t and2_work_bytes(int64_t Q) { return AND2_WORK_HEAD + Q * int64_t(sizeof(QueryProg) + 16 + 8); }
+bool launch_and2_total(const QueryProg* progs, int Q, const ViewDev* views, int V, int S, const int64_t* ti,
+                       int64_t* out, int64_t nout, uint2* pairs, int32_t* partial, uint8_t* work, int cq,
+                       int variant, hipStream_t st);
 // BSI predicate -> one bitmap container per (shard, key): payload u16[S*16*4096], meta int64[S*16].
 // op: 0 EQ, 1 NEQ, 2 LT, 3 LTE, 4 GT, 5 GTE, 6 BETWEEN, 7 NOT NULL (values are base-relative).
 // out_count != nullptr: only add the matching column count (no view is written).

@@ -113,8 +113,17 @@
 // prologue copies the count into its partial.  kbench, min of 10, variant 63
 // alternated three times: no table 15.12-15.15 ms; H = 128 / 256 / 512: 9.95 /
 // 8.08 / 6.46 ms with 28 / 44 / 59 % of the (shard, query) entries precounted.
-// The precounted queries still occupy their lanes of the grid (compaction: a
-// later change).
+// Compaction (profiles/pair_compact/): those precounted queries kept their
+// lanes of the grid -- 16 pairs entries each per shard, a partial, and with
+// 26.9 live lanes per 64-query wave almost no wave was skipped.  For batches
+// above the serving sizes pair_split_kernel now partitions the programs on the
+// device into the live ones and the ones a table answers in EVERY shard;
+// hot_pair_sum_kernel sums the latter from the table and pair_build, the pair
+// kernel (template flag DQ) and the scatter run over the live count, which they
+// read from device memory: 27 waves per (shard, key) unit instead of 62 on the
+// headline batch, 0.42 of the pairs / partial columns.  The PRECOUNTED entries
+// remain for serving-size batches, the per-shard route and views with a
+// written shard's slice masked.
 //
 // Reference hot loops replaced: roaring/roaring.go:3078-3215 intersectionCount*
 // and executor.go:1230-1290 (executeCount over executeIntersect).
@@ -148,9 +157,9 @@ __global__ __launch_bounds__(256) void keymask_build_kernel(ViewDev v, int S, ui
   out[t] = uint16_t(row_keys(v, s, d, lo));
 }
 
-__global__ __launch_bounds__(256) void pair_build_kernel(const QueryProg* __restrict__ progs, int Q,
-                                                         const ViewDev* __restrict__ views, int S,
-                                                         uint2* __restrict__ pairs, int hot) {
+__device__ __forceinline__ void pair_build_body(const QueryProg* __restrict__ progs, int Q,
+                                                const ViewDev* __restrict__ views, int S,
+                                                uint2* __restrict__ pairs, int hot) {
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= int64_t(Q) * S) return;
   const int s = int(t / Q), q = int(t % Q);
@@ -186,6 +195,22 @@ __global__ __launch_bounds__(256) void pair_build_kernel(const QueryProg* __rest
     }
     dst[int64_t(j) * Q] = e;
   }
+}
+
+__global__ __launch_bounds__(256) void pair_build_kernel(const QueryProg* __restrict__ progs, int Q,
+                                                         const ViewDev* __restrict__ views, int S,
+                                                         uint2* __restrict__ pairs, int hot) {
+  pair_build_body(progs, Q, views, S, pairs, hot);
+}
+
+// The compacted route (pair_split_kernel below): the query count *nq is only
+// known on the device.  The grid is sized by the host's count; threads past
+// *nq * S exit before anything is divided by it (*nq may be 0).
+__global__ __launch_bounds__(256) void pair_build_dq_kernel(const QueryProg* __restrict__ progs,
+                                                            const int32_t* __restrict__ nq,
+                                                            const ViewDev* __restrict__ views, int S,
+                                                            uint2* __restrict__ pairs, int hot) {
+  pair_build_body(progs, *nq, views, S, pairs, hot);
 }
 
 // ---- container primitives (wave-cooperative, lb = wave-private 1024-word LDS bitmap)
@@ -588,17 +613,42 @@ __device__ __forceinline__ void twin_swap(const ViewDev& v, int64_t d, int S, in
   m = meta_as_bitmap(m);
 }
 
+// The pair kernel's query count: an int by value, as the kernel has always
+// taken it (same kernel arguments, same code), or with DQ read from device
+// memory.
+template <bool DQ>
+struct QCount {
+  int q;
+  __device__ __forceinline__ int get() const { return q; }
+};
+template <>
+struct QCount<true> {
+  const int32_t* q;
+  __device__ __forceinline__ int get() const { return *q; }
+};
+
 // ---- v6: one wave per (shard, key, chunk of CQ queries).  BST = batched
 // array staging (stage(), the serving variant 39); TWN = bitmap twins on side
-// A (1), side B (2) or both (3, variant 63).
-template <int CQ, bool BST = false, int TWN = 0>
-__global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* __restrict__ progs, int Q,
+// A (1), side B (2) or both (3, variant 63).  DQ = the query count is read from
+// device memory (the compacted route): the grid is sized by the host's count,
+// which is not smaller; the workgroups past the live ones exit first thing and
+// the XCD remap runs over the live ones only (over the whole grid it would
+// hand all live units to the first few XCDs).
+template <int CQ, bool BST = false, int TWN = 0, bool DQ = false>
+__global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* __restrict__ progs, QCount<DQ> qc,
                                                              const ViewDev* __restrict__ views, int S,
                                                              const uint2* __restrict__ pairs,
                                                              int32_t* __restrict__ partial) {
   __shared__ uint64_t lb[1024];
   const int lane = wave_lane();
-  const int64_t gw = int64_t(xcd_remap(blockIdx.x, gridDim.x));
+  const int Q = qc.get();
+  uint32_t nblk = gridDim.x;
+  if (DQ) {
+    const int64_t live = int64_t(S) * 16 * ((Q + CQ - 1) / CQ);   // *nq == 0: every workgroup exits
+    if (int64_t(blockIdx.x) >= live) return;
+    nblk = uint32_t(live);
+  }
+  const int64_t gw = int64_t(xcd_remap(blockIdx.x, nblk));
   const int nch = (Q + CQ - 1) / CQ;
   const int64_t u = gw / nch;
   if (u >= int64_t(S) * 16) return;
@@ -677,6 +727,126 @@ __global__ __launch_bounds__(64, 5) void and2_pairs_v6_kernel(const QueryProg* _
   }
   if (lane < nq) partial[u * Q + q0 + lane] = mine;
 }
+
+// ---- compaction: the queries a hot-pair table answers in every shard leave
+// the pair grid.  pair_split_kernel partitions the sorted KIND_AND2 programs on
+// the device (so every prepare route, the mesh and the alias dedupe get it
+// unchanged and no host copy of the slot map has to follow the writes) into
+//   live  compact copies of the programs the pair kernels still count (order
+//         kept: runs of equal leaf 0 stay contiguous) + their submission indices
+//   hot   {view, min slot, max slot, query} of the table-answered ones, summed
+//         over the shards by hot_pair_sum_kernel, one wave each
+// and leaves both counts in cnt[0] / cnt[1] for the kernels behind it (DQ).
+// A query is table-answered when its rows are two slotted rows of one view
+// whose table is valid in EVERY shard; with any shard masked by a write the
+// view's queries stay live and pair_build's PRECOUNTED branch serves the valid
+// shards as it does on the per-shard route and for small batches.
+constexpr int SPLIT_T = 1024, SPLIT_W = SPLIT_T / 64, SPLIT_MAXV = 64;
+
+__global__ __launch_bounds__(SPLIT_T) void pair_split_kernel(const QueryProg* __restrict__ progs, int Q,
+                                                             const ViewDev* __restrict__ views, int V, int S,
+                                                             const int64_t* __restrict__ ti,
+                                                             QueryProg* __restrict__ lprogs,
+                                                             int64_t* __restrict__ lti, int4* __restrict__ hotl,
+                                                             int32_t* __restrict__ cnt) {
+  __shared__ int vok[SPLIT_MAXV];
+  __shared__ int wl[SPLIT_W], wh[SPLIT_W];
+  __shared__ int dst[SPLIT_T];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  // views past SPLIT_MAXV: their queries stay live
+  const int nv = min(V, SPLIT_MAXV);
+  if (tid < nv)
+    vok[tid] = views[tid].hot_counts != nullptr && views[tid].hot_slot != nullptr && views[tid].hot_valid != nullptr;
+  __syncthreads();
+  for (int v = 0; v < nv; v++) {
+    if (!vok[v]) continue;   // only ever cleared below: a stale 1 costs a redundant look
+    const auto hv = gp(views[v].hot_valid);
+    for (int s = tid; s < S; s += SPLIT_T)
+      if (!hv[s]) vok[v] = 0;
+  }
+  __syncthreads();
+  int lbase = 0, hbase = 0;
+  for (int q0 = 0; q0 < Q; q0 += SPLIT_T) {
+    const int q = q0 + tid;
+    bool hot = false;
+    int4 he = make_int4(0, 0, 0, 0);
+    if (q < Q) {
+      const QueryProg& qp = progs[q];
+      const int va = qp.leaf_view[0];
+      const int64_t ra = qp.leaf_row[0], rb = qp.leaf_row[1];
+      if (va == qp.leaf_view[1] && va >= 0 && va < nv && vok[va] && ra >= 0 && rb >= 0) {
+        const auto hs = gp(views[va].hot_slot);
+        const int sa = hs[ra], sb = hs[rb];
+        if (sa >= 0 && sb >= 0) {
+          hot = true;
+          he = make_int4(va, min(sa, sb), max(sa, sb), q);
+        }
+      }
+    }
+    const bool live = q < Q && !hot;
+    const uint64_t bl = __ballot(live), bh = __ballot(hot);
+    if (lane == 0) {
+      wl[wv] = __popcll(bl);
+      wh[wv] = __popcll(bh);
+    }
+    __syncthreads();
+    int pl = 0, ph = 0, tl = 0, th = 0;
+#pragma unroll
+    for (int w = 0; w < SPLIT_W; w++) {
+      pl += w < wv ? wl[w] : 0;
+      ph += w < wv ? wh[w] : 0;
+      tl += wl[w];
+      th += wh[w];
+    }
+    const uint64_t below = (1ull << lane) - 1;
+    int d = -1;
+    if (live) {
+      d = lbase + pl + __popcll(bl & below);
+      lti[d] = ti[q];
+    }
+    if (hot) hotl[hbase + ph + __popcll(bh & below)] = he;
+    dst[tid] = d;
+    __syncthreads();
+    // the tile's live programs, 16 B per thread and step
+    const uint4* src = reinterpret_cast<const uint4*>(progs + q0);
+    uint4* out = reinterpret_cast<uint4*>(lprogs);
+    const int n16 = min(SPLIT_T, Q - q0) * int(sizeof(QueryProg) / 16);
+    for (int i = tid; i < n16; i += SPLIT_T) {
+      const int dq = dst[i >> 4];
+      if (dq >= 0) out[int64_t(dq) * 16 + (i & 15)] = src[i];
+    }
+    __syncthreads();   // dst, wl, wh are rewritten by the next tile
+    lbase += tl;
+    hbase += th;
+  }
+  if (tid == 0) {
+    cnt[0] = lbase;
+    cnt[1] = hbase;
+  }
+}
+static_assert(sizeof(QueryProg) == 16 * 16, "pair_split_kernel copies a program as 16 uint4");
+
+// One wave per table-answered query: out[ti[query]] += the table's count of
+// its slot pair summed over the shards.  Grid sized by the host's query count.
+__global__ __launch_bounds__(256) void hot_pair_sum_kernel(const ViewDev* __restrict__ views, int S,
+                                                           const int4* __restrict__ hotl,
+                                                           const int32_t* __restrict__ cnt,
+                                                           const int64_t* __restrict__ ti,
+                                                           unsigned long long* __restrict__ out, int64_t nout) {
+  const int w = int(blockIdx.x) * 4 + int(threadIdx.x >> 6);
+  if (w >= cnt[1]) return;
+  const int lane = wave_lane();
+  const int4 e = hotl[w];
+  const ViewDev& hv = views[e.x];
+  const int64_t h = hv.hot_h;
+  const auto hc = gp(hv.hot_counts) + int64_t(e.y) * h + e.z;
+  int64_t a = 0;
+#pragma unroll 4
+  for (int s = lane; s < S; s += 64) a += uint32_t(hc[int64_t(s) * h * h]);
+  a = wave_sum_i64(a);
+  const int64_t o = ti[e.w];
+  if (lane == 0 && a && o >= 0 && o < nout) atomicAdd(out + o, (unsigned long long)a);
+}
 }  // namespace
 
 void launch_twin_build(const ViewDev& v, int S, const int32_t* rows, int R, uint64_t* twin, hipStream_t st) {
@@ -696,8 +866,17 @@ template <int CQ, bool BST, int TWN>
 void launch_v6(const QueryProg* progs, int Q, const ViewDev* views, int S, const uint2* pairs, int32_t* partial,
                hipStream_t st) {
   const int64_t wv = int64_t(S) * 16 * ((Q + CQ - 1) / CQ);
-  hipLaunchKernelGGL((and2_pairs_v6_kernel<CQ, BST, TWN>), dim3(unsigned(wv)), dim3(64), 0, st, progs, Q, views, S,
-                     pairs, partial);
+  hipLaunchKernelGGL((and2_pairs_v6_kernel<CQ, BST, TWN>), dim3(unsigned(wv)), dim3(64), 0, st, progs, QCount<false>{Q},
+                     views, S, pairs, partial);
+}
+
+// the same over *nq <= Q queries (and2_pairs_v6_kernel, DQ)
+template <int CQ, int TWN>
+void launch_v6_dq(const QueryProg* progs, int Q, const int32_t* nq, const ViewDev* views, int S, const uint2* pairs,
+                  int32_t* partial, hipStream_t st) {
+  const int64_t wv = int64_t(S) * 16 * ((Q + CQ - 1) / CQ);
+  hipLaunchKernelGGL((and2_pairs_v6_kernel<CQ, false, TWN, true>), dim3(unsigned(wv)), dim3(64), 0, st, progs,
+                     QCount<true>{nq}, views, S, pairs, partial);
 }
 
 // pair_build then the pair kernel.  `variant`: 63 = bitmap twins (64 queries
@@ -745,10 +924,9 @@ void launch_and2_pairs(const QueryProg* progs, int Q, const ViewDev* views, int 
 // Replaces a strided torch reduction (~67 us for a 36-query serving batch,
 // profiles/r05_serve/) plus an index_copy.  Block = 64 columns x 4 row lanes
 // over a 128-row chunk; one int64 atomic per (block, column).
-__global__ __launch_bounds__(256) void partial_sum_scatter_kernel(const int32_t* __restrict__ partial, int64_t U,
-                                                                  int n, const int64_t* __restrict__ ti,
-                                                                  unsigned long long* __restrict__ out,
-                                                                  int64_t nout) {
+__device__ __forceinline__ void partial_sum_scatter_body(const int32_t* __restrict__ partial, int64_t U, int n,
+                                                         const int64_t* __restrict__ ti,
+                                                         unsigned long long* __restrict__ out, int64_t nout) {
   __shared__ long long acc[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int q = int(blockIdx.x) * 64 + tx;
@@ -768,12 +946,70 @@ __global__ __launch_bounds__(256) void partial_sum_scatter_kernel(const int32_t*
   }
 }
 
+__global__ __launch_bounds__(256) void partial_sum_scatter_kernel(const int32_t* __restrict__ partial, int64_t U,
+                                                                  int n, const int64_t* __restrict__ ti,
+                                                                  unsigned long long* __restrict__ out,
+                                                                  int64_t nout) {
+  partial_sum_scatter_body(partial, U, n, ti, out, nout);
+}
+
+// n = *nq columns (the compacted route); workgroups of columns past it exit whole
+__global__ __launch_bounds__(256) void partial_sum_scatter_dq_kernel(const int32_t* __restrict__ partial, int64_t U,
+                                                                     const int32_t* __restrict__ nq,
+                                                                     const int64_t* __restrict__ ti,
+                                                                     unsigned long long* __restrict__ out,
+                                                                     int64_t nout) {
+  const int n = *nq;
+  if (int(blockIdx.x) * 64 >= n) return;
+  partial_sum_scatter_body(partial, U, n, ti, out, nout);
+}
+
 void launch_partial_sum_scatter(const int32_t* partial, int64_t U, int n, const int64_t* ti, int64_t* out,
                                 int64_t nout, hipStream_t st) {
   if (U <= 0 || n <= 0) return;
   const dim3 grid(unsigned((n + 63) / 64), unsigned((U + 127) / 128));
   hipLaunchKernelGGL(partial_sum_scatter_kernel, grid, dim3(256), 0, st, partial, U, n, ti,
                      reinterpret_cast<unsigned long long*>(out), nout);
+}
+
+// Count(Intersect) totals of a sorted KIND_AND2 part with the table-answered
+// queries compacted out of the pair grid: split -> hot sum -> pair_build ->
+// pair kernel -> scatter, the last three over the live count in work.
+// Variant and queries per wave follow the host's Q as in launch_and2_pairs
+// (the host does not know the live count); only the 32- and 64-query shapes
+// of variants 6 and 63 exist with a device count.  false: nothing launched
+// (serving-size batch, or a shape that is not built).
+bool launch_and2_total(const QueryProg* progs, int Q, const ViewDev* views, int V, int S, const int64_t* ti,
+                       int64_t* out, int64_t nout, uint2* pairs, int32_t* partial, uint8_t* work, int cq,
+                       int variant, hipStream_t st) {
+  if (Q <= 128 || S <= 0 || V <= 0) return false;
+  const bool twin = variant == 63 && (cq > 0 ? cq == 64 : Q > 2048);
+  if (variant == 63 && !twin) variant = 6;
+  if (variant != 6 && !twin) return false;
+  if (cq <= 0) cq = Q <= 2048 ? 32 : 64;
+  if (cq != 32 && cq != 64) return false;
+  int32_t* cnt = reinterpret_cast<int32_t*>(work);
+  QueryProg* lprogs = reinterpret_cast<QueryProg*>(work + AND2_WORK_HEAD);
+  int4* hotl = reinterpret_cast<int4*>(work + AND2_WORK_HEAD + int64_t(Q) * sizeof(QueryProg));
+  int64_t* lti = reinterpret_cast<int64_t*>(work + AND2_WORK_HEAD + int64_t(Q) * (sizeof(QueryProg) + 16));
+  unsigned long long* o64 = reinterpret_cast<unsigned long long*>(out);
+  hipLaunchKernelGGL(pair_split_kernel, dim3(1), dim3(SPLIT_T), 0, st, progs, Q, views, V, S, ti, lprogs, lti, hotl,
+                     cnt);
+  hipLaunchKernelGGL(hot_pair_sum_kernel, dim3(unsigned((Q + 3) / 4)), dim3(256), 0, st, views, S, hotl, cnt, ti,
+                     o64, nout);
+  const int64_t items = int64_t(Q) * S;
+  hipLaunchKernelGGL(pair_build_dq_kernel, dim3(unsigned((items + 255) / 256)), dim3(256), 0, st, lprogs, cnt, views,
+                     S, pairs, 1);
+  if (twin)
+    launch_v6_dq<64, 3>(lprogs, Q, cnt, views, S, pairs, partial, st);
+  else if (cq == 64)
+    launch_v6_dq<64, 0>(lprogs, Q, cnt, views, S, pairs, partial, st);
+  else
+    launch_v6_dq<32, 0>(lprogs, Q, cnt, views, S, pairs, partial, st);
+  const int64_t U = int64_t(S) * 16;
+  const dim3 grid(unsigned((Q + 63) / 64), unsigned((U + 127) / 128));
+  hipLaunchKernelGGL(partial_sum_scatter_dq_kernel, grid, dim3(256), 0, st, partial, U, cnt, lti, o64, nout);
+  return true;
 }
 
 }  // namespace pk

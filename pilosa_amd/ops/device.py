@@ -1312,6 +1312,11 @@ class DeviceRowBlock:
 class GpuEngine:
     """Batched query execution on one GPU (all views must share the shard list)."""
 
+    # queries of a Count(Intersect) part from which the compacted route runs: the
+    # smallest measured size at which it wins (kbench: 512 queries 1.66 -> 1.45 ms,
+    # 256 queries 0.86 -> 1.05 ms, profiles/pair_compact/)
+    PAIR_COMPACT_MIN = 512
+
     def __init__(self, device):
         import torch
 
@@ -1332,6 +1337,12 @@ class GpuEngine:
         # per-shard hot-pair table by pair_build (DeviceView.ensure_hot); the
         # launcher hands it to the shipped kernels only (v6, 39, 63)
         self.use_hot = os.environ.get("PILOSA_HOTPAIR", "1") != "0"
+        # ... and a part of at least PAIR_COMPACT_MIN queries takes the queries a
+        # table answers in every shard out of the pair grid on the device
+        # (pair_split_kernel, profiles/pair_compact/); serving-size batches
+        # (<= 128 queries) never do
+        self.use_compact = os.environ.get("PILOSA_PAIR_COMPACT", "1") != "0"
+        self.PAIR_COMPACT_MIN = int(os.environ.get("PILOSA_PAIR_COMPACT_MIN", str(self.PAIR_COMPACT_MIN)))
         # Count(Union(leaves)) route: union_count_kernel (bitmap_kernels.hip)
         self.use_union = os.environ.get("PILOSA_UNION_KERNEL", "1") != "0"
         # 2 = union_count2_kernel (flat chunk walk, parallel meta fetch), 1 = union_count_kernel
@@ -1504,7 +1515,7 @@ class GpuEngine:
         dev = self._h2d_many(host)
         tv = dev[0]
         parts = [(dev[1 + 2 * i], dev[2 + 2 * i].view(torch.int64), k, n) for i, (k, n) in enumerate(meta)]
-        return (Q, S, tv, parts, shd)
+        return (Q, S, tv, parts, shd, bool(varr["hot_counts"].any()))
 
     def prepare_planned(self, Q: int, segs, buf: np.ndarray, views: List["DeviceView"], S: int):
         """:meth:`prepare_progs` for a batch planned natively
@@ -1531,7 +1542,7 @@ class GpuEngine:
                               int(n)))
                 continue
             parts.append((tb[po:po + n * QPROG_DTYPE.itemsize], tb[oo:oo + n * 8].view(torch.int64), int(kind), int(n)))
-        return (Q, S, tv, parts, shd)
+        return (Q, S, tv, parts, shd, bool(varr["hot_counts"].any()))
 
     @staticmethod
     def _hot_leaf_first(progs: np.ndarray, sel: np.ndarray) -> np.ndarray:
@@ -1564,6 +1575,31 @@ class GpuEngine:
             variant = 63
         self.ext.and2_count(tp, tv, S, pairs, partial, self.and2_cq, variant)
         return partial.view(S, 16, n)
+
+    def _compact_route(self, n: int) -> bool:
+        """Whether a Count(Intersect) part of ``n`` queries whose batch passes a
+        hot-pair table runs with the table-answered queries compacted out of
+        the pair grid.  Only the 32- and 64-query shapes of variants 6 and 63
+        exist with a device-resident query count, and never a serving-size
+        batch: the three kernels the route adds would be a measurable share
+        of its 0.2 ms."""
+        return self.use_compact and self.use_hot and self.and2_variant in (6, 63) and \
+            n > 128 and n >= self.PAIR_COMPACT_MIN and (self.and2_cq <= 0 or self.and2_cq in (32, 64))
+
+    def _and2_total(self, tp, tv, S: int, n: int, ti, out, shd: int = 0):
+        """out[ti[q]] += Count(Intersect) of the part's n sorted programs, one
+        launch sequence on the current stream (split, table sums, pair_build,
+        pair kernel, scatter).  Variant and queries per wave are chosen from
+        n as in :meth:`_and2_partial`: the host does not know how many queries
+        stay live."""
+        torch = self.torch
+        pairs = torch.empty(S * 16 * n * 2, dtype=torch.int32, device=self.device)
+        partial = torch.empty(S * 16 * n, dtype=torch.int32, device=self.device)
+        work = torch.empty(self.ext.and2_work_bytes(n), dtype=torch.uint8, device=self.device)
+        variant = self.and2_variant
+        if variant == 6 and shd == 2 and self.use_twin:
+            variant = 63
+        self.ext.and2_count_total(tp, tv, S, ti, out, pairs, partial, work, self.and2_cq, variant)
 
     def to_host(self, t):
         with tracing.span("GpuEngine.d2h", gpu=True):
@@ -1600,10 +1636,14 @@ class GpuEngine:
         torch = self.torch
         Q, S, tv, parts = handle[:4]
         shd = len(handle) > 4 and handle[4]
+        tabled = len(handle) > 5 and handle[5]      # some view of the batch passes a hot-pair table
         out = torch.zeros(Q, dtype=torch.int64, device=self.device)
         for tp, ti, kind, n in parts:
             if kind == KIND_ALIAS:   # repeated calls: their answers copied (the last part)
                 out.index_copy_(0, ti, out.index_select(0, tp))
+                continue
+            if kind == KIND_AND2 and tabled and self._compact_route(n):
+                self._and2_total(tp, tv, S, n, ti, out, shd)
                 continue
             if kind == KIND_AND2:
                 # column sums scattered into out by one kernel (a strided torch

@@ -30,7 +30,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFILT = os.environ.get("CXXFILT", "c++filt")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S"]
 # template name -> {number of template arguments: positions of the identifying ones}
-TEMPLATE_KEYS = {"and2_pairs_v6_kernel": {11: (0, 6, 9), 3: (0, 1, 2)}}   # (CQ, BST, TWN)
+TEMPLATE_KEYS = {"and2_pairs_v6_kernel": {11: (0, 6, 9), 3: (0, 1, 2), 4: (0, 1, 2, 3)}}   # (CQ, BST, TWN[, DQ])
+# template name -> number of identifying arguments a revision without the later ones has: trailing
+# arguments past it are dropped from the key while they are 0 (the instantiations that revision had)
+TRAILING_FLAGS = {"and2_pairs_v6_kernel": 3}
 RENAMED = {"shadow_build_kernel": "twin_build_kernel"}
 STATS = (("vgpr", "NumVgprs"), ("sgpr", "TotalNumSgprs"), ("lds", "LDSByteSize"), ("scratch", "ScratchSize"))
 
@@ -63,6 +66,8 @@ def key_of(mangled):
     pos = TEMPLATE_KEYS.get(base, {}).get(len(args))
     norm = {"false": "0", "true": "1"}
     args = [norm.get(args[p], args[p]) for p in pos] if pos else args
+    while base in TRAILING_FLAGS and len(args) > TRAILING_FLAGS[base] and args[-1] == "0":
+        args.pop()
     return RENAMED.get(base, base) + ("<" + ", ".join(args) + ">" if args else "")
 
 

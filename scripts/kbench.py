@@ -9,8 +9,12 @@ bitmap twins (64 queries per wave); --twin-cutoff lists the cutoffs T variant
 63 is timed at (the twin is rebuilt per T).  A variant may be listed several
 times to alternate it with others.  --hot-rows times the kernels with the
 hot-pair table of H rows (DeviceView.ensure_hot) next to H = 0 on the same
-arena, and prints how many entries it answers.  The pair kernels are the same
-in both modules; PILOSA_HIPKERNELS=_hipkernels runs the shipped one."""
+arena, and prints how many entries it answers.  --compact 0,1 alternates
+today's route and the one that compacts the table-answered queries out of the
+pair grid (GpuEngine.use_compact) for every such setting, in one process on one
+arena; --row-mod 512 draws every row from the table's rows (a batch with no
+live query: the compacted route's oversized-grid tail).  The pair kernels are
+the same in both modules; PILOSA_HIPKERNELS=_hipkernels runs the shipped one."""
 import argparse
 import json
 import math
@@ -41,6 +45,9 @@ def main():
                     "(default: DeviceView.TWIN_CUTOFF)")
     ap.add_argument("--hot-rows", default="", help="hot-pair table sizes H each --variants setting of the shipped "
                     "kernels (6, 39, 63) is timed at, e.g. 0,128,256,512 (0 = no table; default: no table)")
+    ap.add_argument("--compact", default="", help="0,1: time each --variants setting on today's route (0) and "
+                    "with the table-answered queries compacted out of the pair grid (1); default: the engine's own")
+    ap.add_argument("--row-mod", type=int, default=0, help="take the batch's row ids modulo this (0 = as drawn)")
     args = ap.parse_args()
     import torch
 
@@ -55,6 +62,8 @@ def main():
     del arena
     rng = np.random.default_rng(1234)
     ra, rb = zipf_rows(rng, args.batch), zipf_rows(rng, args.batch)
+    if args.row_mod:
+        ra, rb = ra % args.row_mod, rb % args.row_mod
     qs = [f"Count(Intersect(Row(f={a}), Row(f={b})))" for a, b in zip(ra, rb)]
     progs, views, S = NativeCountCompiler({"f": view}).compile(qs)
     results = {}
@@ -69,16 +78,21 @@ def main():
         cq = int(cq) if cq else cq0
         cuts = [int(t) for t in args.twin_cutoff.split(",") if t] if int(vv) == 63 else []
         hots = [int(h) for h in args.hot_rows.split(",") if h] if int(vv) in (6, 39, 63) else []
+        compacts = [int(c) for c in args.compact.split(",") if c]
         for t in cuts or [None]:
             for hr in hots or [0]:
-                name = f"and2var{vv}_cq{cq}" + (f"_t{t}" if t is not None else "") + (f"_h{hr}" if hr else "")
-                while name in [c[0] for c in configs]:
-                    name += "'"      # a repeat of the same setting (alternating runs)
-                configs.append((name, {"and2_cq": cq, "and2_variant": int(vv), "twin_cutoff": t, "hot_rows": hr}))
+                for cp in compacts or [None]:
+                    name = f"and2var{vv}_cq{cq}" + (f"_t{t}" if t is not None else "") + (f"_h{hr}" if hr else "") + \
+                        (f"_c{cp}" if cp is not None else "")
+                    while name in [c[0] for c in configs]:
+                        name += "'"      # a repeat of the same setting (alternating runs)
+                    configs.append((name, {"and2_cq": cq, "and2_variant": int(vv), "twin_cutoff": t, "hot_rows": hr,
+                                           "compact": cp}))
     for name, cfg in configs:
         eng = GpuEngine(dev)
         cut = cfg.pop("twin_cutoff", None)
         hot = cfg.pop("hot_rows", 0)
+        compact = cfg.pop("compact", None)
         for k, v in cfg.items():
             setattr(eng, k, v)
         eng.use_twin = cfg.get("and2_variant") == 63   # variants are explicit here: 6 is the plain kernel
@@ -86,6 +100,9 @@ def main():
             view._twin = None        # rebuilt at this cutoff by prepare_progs
             view.TWIN_CUTOFF = cut
         eng.use_hot = hot > 0        # the table is explicit too
+        if compact is not None:      # and so is the route: any batch above the serving sizes
+            eng.use_compact = bool(compact)
+            eng.PAIR_COMPACT_MIN = 1
         if hot and (view.HOTPAIR_ROWS != hot or getattr(view, "_hot", None) is None):
             view._hot = None         # rebuilt at this size by prepare_progs
             view.HOTPAIR_ROWS = hot

@@ -12,6 +12,11 @@ from the per-shard count table whenever both rows of a query are among them,
 what remains in the pair kernel as a share of today -- queries answered,
 pairs, array probes, bitmap / twin B pairs, stagings, referenced bytes (twins
 at --hot-twin-cutoff, the planner's dedupe ignored).
+Compaction ("compaction", per H, repeated queries removed as the planner
+does): the columns of a (shard, key) unit's pairs / partial rows and its
+64-query waves today and with the table-answered queries taken out of the
+grid, the live lanes per wave, and the run lengths of equal leaf 0 among the
+live queries (a run of one is a staging no other query shares).
 Usage: python scripts/pair_stats.py [--sample 2] [--batch 4096] [--twin-cutoff 3072,2730,2048]
        [--hot-rows 64,128,256,512,1024] [--seed 1234]"""
 import argparse
@@ -84,6 +89,28 @@ def main():
     dB = np.array([dense.get(int(r), -1) for r in B])
     for h in hots:
         hot[h]["queries_answered"] = int(sum(1 for a, b in zip(dA, dB) if a in hot_set[h] and b in hot_set[h]))
+
+    # compaction: query-level, the same for every (shard, key) unit
+    uq = np.unique(np.stack([dA, dB], axis=1), axis=0)     # sorted by (A, B), duplicates removed
+    compaction = {}
+    for h in hots:
+        hs = np.fromiter(hot_set[h], np.int64)
+        live = ~(np.isin(uq[:, 0], hs) & np.isin(uq[:, 1], hs))
+        waves = [live[c0:c0 + args.cq] for c0 in range(0, len(uq), args.cq)]
+        la = uq[live, 0]
+        starts = np.flatnonzero(np.concatenate([[True], la[1:] != la[:-1]])) if len(la) else np.zeros(0, np.int64)
+        lens = np.diff(np.concatenate([starts, [len(la)]]))
+        nl = int(live.sum())
+        wc = -(-nl // args.cq)
+        hist = collections.Counter(int(min(x, 64)) for x in lens)
+        compaction[str(h)] = {
+            "queries_in_grid": {"today": len(uq), "compacted": nl},
+            "waves_per_unit": {"today": len(waves), "entirely_table_answered": int(sum(1 for w in waves if not w.any())),
+                               "compacted": wc},
+            "live_lanes_per_wave": {"today": round(nl / max(len(waves), 1), 1), "compacted": round(nl / max(wc, 1), 1)},
+            "live_runs": int(len(lens)), "live_one_off_runs": int((lens == 1).sum()),
+            "live_run_length_hist": {str(k): v for k, v in sorted(hist.items())},
+        }
 
     def size_class(x):
         for b in (512, 1024, 2048, 2730):
@@ -194,6 +221,7 @@ def main():
                                          (c["twin_B_pairs"] + c["bitmap_B_pairs"]) /
                                          max(today["twin_B_pairs"] + today["bitmap_B_pairs"], 1), 4))
                         for h, c in hot.items() if h}
+    out["compaction"] = compaction
     rl = sorted(runlen.items())
     out["run_length_hist"] = {k: round(v * f) for k, v in rl}
     out["one_off_runs"] = round(runlen[1] * f)
