@@ -333,6 +333,47 @@ int64_t bsi_distinct(torch::Tensor progs, torch::Tensor views, int64_t S, torch:
   return n;
 }
 
+// Extract: columns / values / valid of the filter's columns in ascending order (see kernels.h); columns may be
+// empty (not written); returns the tile slots per workgroup used
+int64_t bsi_extract(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor bsi_args, int64_t slots,
+                    torch::Tensor unit_off, torch::Tensor col_base, int64_t base, torch::Tensor columns,
+                    torch::Tensor values, torch::Tensor valid) {
+  check_dev(progs, "progs");
+  check_dev(views, "views");
+  check_dev(unit_off, "unit_off");
+  check_dev(col_base, "col_base");
+  check_dev(values, "values");
+  check_dev(valid, "valid");
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24), "bsi_extract: shard count");
+  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  const pk::BsiArgs b = bsi_args_from(bsi_args);
+  TORCH_CHECK(b.depth >= 0 && b.depth <= pk::EXTRACT_MAX_PLANES, "bsi_extract: bit depth");
+  TORCH_CHECK(b.view >= 0 && int64_t(b.view) < views.numel() / int64_t(sizeof(pk::ViewDev)), "bsi_extract: view slot");
+  TORCH_CHECK(unit_off.scalar_type() == torch::kInt64 && unit_off.is_contiguous() && unit_off.numel() >= S * 16,
+              "unit_off must be int64[S * 16]");
+  TORCH_CHECK(col_base.scalar_type() == torch::kInt64 && col_base.is_contiguous() && col_base.numel() >= S,
+              "col_base must be int64[S]");
+  const int64_t cap = values.numel();
+  TORCH_CHECK(values.scalar_type() == torch::kInt64 && values.is_contiguous(), "values must be int64[cap]");
+  TORCH_CHECK(valid.scalar_type() == torch::kUInt8 && valid.is_contiguous() && valid.numel() == cap,
+              "valid must be uint8[cap]");
+  uint64_t* cols = nullptr;
+  if (columns.numel()) {
+    check_dev(columns, "columns");
+    TORCH_CHECK(columns.scalar_type() == torch::kInt64 && columns.is_contiguous() && columns.numel() == cap,
+                "columns must be int64[cap] or empty");
+    cols = reinterpret_cast<uint64_t*>(columns.data_ptr<int64_t>());
+  }
+  const int n = pk::launch_bsi_extract(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
+                                       reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+                                       int(slots), unit_off.data_ptr<int64_t>(), col_base.data_ptr<int64_t>(), base,
+                                       cap, cols, values.data_ptr<int64_t>(), valid.data_ptr<uint8_t>(),
+                                       cur_stream(views));
+  TORCH_CHECK(n > 0, "bsi_extract: not launched");
+  check_launch("bsi_extract");
+  return n;
+}
+
 void bsi_minmax_fold(torch::Tensor o, int64_t F, int64_t G, int64_t is_min, torch::Tensor out) {
   check_dev(o, "o");
   check_dev(out, "out");
@@ -1240,6 +1281,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsi_distinct", &bsi_distinct, "Distinct: mark the magnitudes of exists & filter in the pos / neg bitmaps");
   m.def("distinct_slots", [](int64_t depth, int64_t want) { return int64_t(pk::distinct_slots(int(depth), int(want))); },
         "Distinct: tile slots per workgroup the launcher uses for this depth and request");
+  m.def("bsi_extract", &bsi_extract, "Extract: columns, values and validity of the filter's columns, ascending");
+  m.def("extract_slots", [](int64_t depth, int64_t want) { return int64_t(pk::extract_slots(int(depth), int(want))); },
+        "Extract: tile slots per workgroup the launcher uses for this depth and request");
   m.def("leaf_src", &leaf_src, "src containers of plain rows straight from the arena (TopN srcs)");
   m.def("row_counts", &row_counts, "row counts of (shard, dense row) entries (device rank caches)");
   m.def("topn_cache_counts", &topn_cache_counts, "cache-only TopN: [candidate x shard] row counts");

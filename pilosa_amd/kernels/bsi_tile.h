@@ -1,6 +1,8 @@
 // Per-(shard, key) access to the rows of a BSI view as register tiles: the
-// container lookups and tile loads shared by the BSI kernels (bsi_kernels.hip)
-// and the Distinct kernel (distinct_kernels.hip).  Include after expr_tile.h.
+// container lookups and tile loads shared by the BSI kernels (bsi_kernels.hip),
+// the Distinct kernel (distinct_kernels.hip) and the Extract kernel
+// (extract_kernels.hip), and the slice-wise staging the latter two share.
+// Include after expr_tile.h.
 #pragma once
 #include "expr_tile.h"
 
@@ -67,6 +69,31 @@ __device__ __forceinline__ void bsi_plane(const BsiCtx& c, int lane_slot, Tile& 
 __device__ __forceinline__ void bsi_bit(const BsiCtx& c, int i, Tile& t) {
   if (i < 0 || i >= c.bsi.depth) tile_zero(t);
   else bsi_plane(c, i, t);
+}
+
+// (a native 16-byte vector, moved as ds_*_b128: see bsi_group_sum_kernel)
+typedef uint64_t dq_u64x2 __attribute__((ext_vector_type(2)));
+
+// f(i, word pair) for the slots i in [slot0, slot0 + n) of container m, as the
+// calling lane holds them in a Tile.  i is a constant after unrolling.  A
+// bitmap container loads only those slots; arrays and runs go through lb.
+template <class F>
+__device__ __forceinline__ void slice_each(const uint16_t* payload, int64_t m, uint64_t* lb, int slot0, int n,
+                                           F&& f) {
+  const int lane = wave_lane();
+  if (meta_type(m) == CT_BITMAP) {
+    const ulong2* p = reinterpret_cast<const ulong2*>(payload + meta_off16(m) * 8);
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+      if (i >= slot0 && i < slot0 + n) f(i, p[i * 64 + lane]);
+  } else {
+    lds_expand(lb, payload, m);
+    const ulong2* l2 = reinterpret_cast<const ulong2*>(lb);
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+      if (i >= slot0 && i < slot0 + n) f(i, l2[i * 64 + lane]);
+    lds_fence();
+  }
 }
 
 }  // namespace pk

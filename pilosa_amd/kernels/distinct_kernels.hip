@@ -58,31 +58,6 @@
 
 namespace pk {
 
-// (a native 16-byte vector, moved as ds_*_b128: see bsi_group_sum_kernel)
-typedef uint64_t dq_u64x2 __attribute__((ext_vector_type(2)));
-
-// f(i, word pair) for the slots i in [slot0, slot0 + n) of container m, as the
-// calling lane holds them in a Tile.  i is a constant after unrolling.  A
-// bitmap container loads only those slots; arrays and runs go through lb.
-template <class F>
-__device__ __forceinline__ void slice_each(const uint16_t* payload, int64_t m, uint64_t* lb, int slot0, int n,
-                                           F&& f) {
-  const int lane = wave_lane();
-  if (meta_type(m) == CT_BITMAP) {
-    const ulong2* p = reinterpret_cast<const ulong2*>(payload + meta_off16(m) * 8);
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-      if (i >= slot0 && i < slot0 + n) f(i, p[i * 64 + lane]);
-  } else {
-    lds_expand(lb, payload, m);
-    const ulong2* l2 = reinterpret_cast<const ulong2*>(lb);
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-      if (i >= slot0 && i < slot0 + n) f(i, l2[i * 64 + lane]);
-    lds_fence();
-  }
-}
-
 template <int MARK>
 __device__ __forceinline__ void distinct_mark(uint32_t* __restrict__ bm, uint32_t mag) {
   uint32_t* w = bm + (mag >> 5);

@@ -160,6 +160,22 @@ int distinct_slots(int depth, int want);
 int launch_bsi_distinct(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots, int mark,
                         uint32_t* pos, uint32_t* neg, hipStream_t st);
 
+// Extract(filter, Rows(field=)) (extract_kernels.hip, K27): for every column of
+// the filter progs[0] (nprog >= 1), in ascending column order, columns[o] = the
+// global column id (col_base[s] + the column's offset in arena shard s),
+// values[o] = its real value in the BSI field (base applied; 0 without one),
+// valid[o] = 1 when it has one.  unit_off[s * 16 + j] = the output position of
+// the first column of (shard, key), an exclusive prefix sum of the filter's
+// per-unit counts; -1 = skip the unit.  cap = the length of the output vectors:
+// no store goes past it.  columns == nullptr: leave the column vector alone.
+// depth <= EXTRACT_MAX_PLANES.  slots as for launch_bsi_distinct, clamped by
+// extract_slots().  Returns the slots used, -1 when nothing was launched.
+constexpr int EXTRACT_MAX_PLANES = 32;
+int extract_slots(int depth, int want);
+int launch_bsi_extract(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots,
+                       const int64_t* unit_off, const int64_t* col_base, int64_t base, int64_t cap, uint64_t* columns,
+                       int64_t* values, uint8_t* valid, hipStream_t st);
+
 // TopK(field=, k=) (topk_kernels.hip, K25): out[d] +=|row d ∩ filter| over
 // the S arena shards for every dense row d of ``fv``; the filter is dense row
 // ``xd`` of ``*xv`` (same shard list), staged once per (shard, key) in LDS.

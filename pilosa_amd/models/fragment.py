@@ -795,6 +795,55 @@ class Fragment:
             neg[np.searchsorted(cols, on)] = True
         return np.unique(mags[~neg]), np.unique(mags[neg])
 
+    def _positions(self, row_id: int, want: Row, cols: np.ndarray) -> np.ndarray:
+        """Positions in the ascending ``cols`` (= want's columns) of those in row ``row_id``."""
+        on = self.row(row_id).intersect(want).columns()
+        return np.searchsorted(cols, on) if len(on) else np.zeros(0, np.int64)
+
+    def extract_values(self, columns: np.ndarray, bit_depth: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The base-relative values of the ascending ``columns`` of this shard:
+        (int64 values, bool validity), value 0 where the column holds none.  A
+        per-plane gather like distinct(): every plane's columns inside the set
+        OR their bit into that column's magnitude, so the cost is columns x
+        bit_depth whatever the value range is."""
+        cols = np.asarray(columns, dtype=np.uint64)
+        mags = np.zeros(len(cols), np.uint64)
+        valid = np.zeros(len(cols), bool)
+        if not len(cols):
+            return mags.astype(np.int64), valid
+        want = Row(cols)
+        valid[self._positions(BSI_EXISTS_BIT, want, cols)] = True
+        for i in range(bit_depth):
+            mags[self._positions(BSI_OFFSET_BIT + i, want, cols)] |= np.uint64(1 << i)
+        vals = mags.astype(np.int64)
+        neg = self._positions(BSI_SIGN_BIT, want, cols)
+        vals[neg] = -vals[neg]
+        vals[~valid] = 0
+        return vals, valid
+
+    def extract_rows(self, columns: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """The rows holding each of the ascending ``columns`` of this shard, as
+        CSR: (int64 offsets[len + 1], uint64 rows), the rows of a column
+        ascending.  A per-row membership scatter: every row of the fragment is
+        intersected with the set once."""
+        cols = np.asarray(columns, dtype=np.uint64)
+        n = len(cols)
+        if not n:
+            return np.zeros(1, np.int64), np.zeros(0, np.uint64)
+        want = Row(cols)
+        pos, ids = [], []
+        for rid in self.rows():
+            p = self._positions(rid, want, cols)
+            if len(p):
+                pos.append(p)
+                ids.append(np.full(len(p), rid, np.uint64))
+        if not pos:
+            return np.zeros(n + 1, np.int64), np.zeros(0, np.uint64)
+        pos, ids = np.concatenate(pos), np.concatenate(ids)
+        order = np.argsort(pos, kind="stable")      # rows were visited ascending
+        offs = np.concatenate([[0], np.cumsum(np.bincount(pos, minlength=n))]).astype(np.int64)
+        return offs, ids[order]
+
     def _min_unsigned(self, filt: Row, bit_depth: int) -> Tuple[int, int]:
         mn, count = 0, 0
         for i in range(bit_depth - 1, -1, -1):

@@ -2118,6 +2118,76 @@ class GpuEngine:
         neg = idx[wi] >= words
         return mags[~neg], mags[neg]
 
+    # bit planes bsi_extract_kernel transposes at most (kernels.h EXTRACT_MAX_PLANES)
+    EXTRACT_MAX_PLANES = 32
+
+    def bsi_extract(self, filt: object, fields: Sequence[Tuple["DeviceView", int, int]], window: Optional[int] = None,
+                    slots: int = 0, guard=None):
+        """The columns of ``filt`` over the local shards, ascending, and their
+        values in the BSI ``fields`` [(view, depth, base)]: (uint64 columns,
+        [(int64 values, bool validity) per field], the filter's count).
+
+        1. one expr_count launch of the filter program: int32 counts per
+           (shard, key);
+        2. a device cumsum: the exclusive offset of every unit; the total and
+           the length of the output -- the end of the last unit that starts
+           inside ``window`` (offset + limit; None: everything) -- are read in
+           one transfer, and ``guard(total)`` (the size guard) runs when there
+           is no window; units that are empty or start beyond the window get
+           offset -1;
+        3. one bsi_extract_kernel launch per field; they share the offsets, and
+           only the first writes the column vector.  The vectors are cut to
+           the window and copied to the host, one transfer each.
+
+        The output vectors are (8 + 9 * fields) bytes per column from torch's
+        caching allocator, per request, outside the arenas' ``hbm_budget``."""
+        torch = self.torch
+        from pilosa_amd import shardwidth
+        bv0 = fields[0][0]
+        S = bv0.S
+        for bv, depth, _ in fields:
+            if depth < 0 or depth > self.EXTRACT_MAX_PLANES:
+                raise NotImplementedError("bit depth beyond the transpose")
+            if bv.S != S:
+                raise NotImplementedError("views over different shards")
+        none = (np.zeros(0, np.uint64), [(np.zeros(0, np.int64), np.zeros(0, bool)) for _ in fields], 0)
+        if not S:
+            return none
+        progs, ordered = self._bsi_filter_program(filt, bv0)
+        tp, tv = self.upload_batch(progs, ordered)
+        counts = torch.zeros(S * 16, dtype=torch.int32, device=self.device)
+        self.ext.expr_count(tp, tv, S, torch.empty(0, dtype=torch.int64, device=self.device), counts,
+                            2 if bool(flat_mask(progs).all()) else 0)
+        c64 = counts.to(torch.int64)
+        ends = torch.cumsum(c64, 0)
+        offs = ends - c64
+        live = c64 > 0
+        if window is not None:
+            live = live & (offs < int(window))
+        last = torch.where(live, ends, torch.zeros_like(ends)).max()
+        total, n_out = self.to_host(torch.stack([ends[-1], last])).tolist()
+        if window is None and guard is not None:
+            guard(int(total))
+        if not n_out:
+            return none[0], none[1], int(total)
+        unit_off = torch.where(live, offs, torch.full_like(offs, -1)).contiguous()
+        col_base = torch.from_numpy(np.asarray(bv0.shards, dtype=np.int64) * shardwidth.ARENA_WIDTH).to(self.device)
+        keep = n_out if window is None else min(n_out, int(window))
+        columns = torch.empty(n_out, dtype=torch.int64, device=self.device)
+        out = []
+        for i, (bv, depth, base) in enumerate(fields):
+            if i:
+                progs, ordered = self._bsi_filter_program(filt, bv)
+                tp, tv = self.upload_batch(progs, ordered)
+            values = torch.empty(n_out, dtype=torch.int64, device=self.device)
+            valid = torch.empty(n_out, dtype=torch.uint8, device=self.device)
+            self.ext.bsi_extract(tp, tv, S, torch.from_numpy(self.bsi_args(bv, depth)), int(slots), unit_off, col_base,
+                                 int(base), columns if i == 0 else columns[:0], values, valid)
+            out.append((values, valid))
+        cols = self.to_host(columns[:keep]).numpy().view(np.uint64)
+        return cols, [(self.to_host(v[:keep]).numpy(), self.to_host(ok[:keep]).numpy().astype(bool))
+                      for v, ok in out], int(total)
+
     def _bsi_minmax_dev(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, which: str = ""):
         torch = self.torch
         S = bsi_view.S

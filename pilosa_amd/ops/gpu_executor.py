@@ -13,6 +13,9 @@ device arenas of the involved field-views:
                 one bsi_kth_step launch per bit (global MSB-first descent)
 * ``bsi_distinct`` Distinct(<filter>, field=f) -> bsi_distinct_kernel (one pass:
                 planes staged per (shard, key, slice), transposed, marked)
+* ``bsi_extract`` Extract(<filter>, Rows(field=f)...) -> expr_count (offsets per
+                (shard, key)) + one bsi_extract_kernel pass per int field
+                (planes staged, transposed, written compacted in column order)
 * ``topk``      TopK(<filter>, field=f, k=n)           -> row_filter_counts (one
                 pass: filter staged per (shard, key), every row streamed past)
 * ``topn``      TopN phase-1/phase-2 with src          -> slot-index LDS
@@ -99,6 +102,22 @@ def distinct_slots_env() -> int:
     except ValueError:
         return DISTINCT_SLOTS_DEFAULT
     return v if v in (1, 2, 4, 8) else DISTINCT_SLOTS_DEFAULT
+
+
+# tile slots per workgroup of bsi_extract_kernel: the default is the fastest
+# measured (profiles/extract/README.md)
+EXTRACT_SLOTS_DEFAULT = 1
+
+
+def extract_slots_env() -> int:
+    """PILOSA_EXTRACT_SLOTS: tile slots per workgroup of bsi_extract_kernel
+    (1, 2, 4 or 8, clamped by the launcher to what fits the LDS at the field's
+    depth); anything else means EXTRACT_SLOTS_DEFAULT."""
+    try:
+        v = int(os.environ.get("PILOSA_EXTRACT_SLOTS", "") or EXTRACT_SLOTS_DEFAULT)
+    except ValueError:
+        return EXTRACT_SLOTS_DEFAULT
+    return v if v in (1, 2, 4, 8) else EXTRACT_SLOTS_DEFAULT
 
 
 class _Empty:
@@ -219,6 +238,7 @@ class GpuExecutor:
         self.group_sum_per_filter = 0   # ... and by the per-filter kernel
         self.percentile_device = 0       # Percentile() calls answered by bsi_percentile (the fast path)
         self.distinct_device = 0         # Distinct() map steps answered by bsi_distinct (K26)
+        self.extract_device = 0          # Extract() (map step, int field) pairs answered by bsi_extract (K27)
         self.topk_device = 0             # TopK() map steps answered by row_filter_counts_kernel
         self.topk_programs = 0           # ... and by the per-row programs route
         # serving Count text path: host prep (parse..launch) vs result wait
@@ -441,6 +461,7 @@ class GpuExecutor:
                 "rowUpdates": self.row_updates, "deviceWrites": self.device_writes,
                 "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
                 "percentileDevice": self.percentile_device, "distinctDevice": self.distinct_device,
+                "extractDevice": self.extract_device,
                 "groupSumDevice": self.group_sum_device,
                 "groupSumPerFilter": self.group_sum_per_filter, "topkDevice": self.topk_device,
                 "topkPrograms": self.topk_programs}
@@ -713,6 +734,48 @@ class GpuExecutor:
         self.distinct_device += 1
         self.launches += 1
         return SignedRow.from_values(np.concatenate([pos.astype(np.int64), -neg.astype(np.int64)]) + b.base)
+
+    def bsi_extract(self, index: str, filt_call: Call, fields, window: Optional[int], shards: List[int]):
+        """Extract(<filter>, Rows(field=)...) over the local shards -> ONE
+        ExtractedTable of the filter's first ``window`` columns (None: all).
+        Routing is per field: an int field of depth <= 32 is answered by
+        bsi_extract_kernel (GpuEngine.bsi_extract: a count pass, a cumsum, one
+        launch per field); every other field -- set, time, mutex, bool, a
+        deeper int field -- by the host function over the device's column
+        vector.  No int field the kernel can take, a filter the planner cannot
+        take or a CompileError leave the whole map step to the host.
+        PILOSA_EXTRACT_SLOTS sets the tile slots per workgroup."""
+        from pilosa_amd.executor import (ExtractedTable, extract_field_type, extract_fields_host, extract_guard)
+        from pilosa_amd.models.field import FIELD_TYPE_INT
+        names = [(f.name, extract_field_type(f)) for f in fields]
+        dev = []
+        for i, f in enumerate(fields):
+            b = f.bsi_group(f.name) if f.type == FIELD_TYPE_INT else None
+            if b is not None and b.bit_depth <= GpuEngine.EXTRACT_MAX_PLANES:
+                bv = self.view_arena(index, f.name, VIEW_BSI_PREFIX + f.name, shards)
+                if bv is not None:
+                    dev.append((i, bv, b.bit_depth, b.base))
+        if not dev:
+            raise NotImplementedError
+        filt = self.plan(index, filt_call, shards)
+        if filt is EMPTY:
+            self.extract_device += len(dev)   # a filter known empty from the schema: no launch
+            return ExtractedTable(names)
+        try:
+            cols, vecs, _ = self.engine.bsi_extract(filt, [d[1:] for d in dev], window, extract_slots_env(),
+                                                    extract_guard)
+        except CompileError:
+            raise NotImplementedError
+        self.extract_device += len(dev)
+        self.launches += 1 + len(dev)
+        data = [None] * len(fields)
+        for (i, *_), vec in zip(dev, vecs):
+            data[i] = vec
+        rest = [i for i in range(len(fields)) if data[i] is None]
+        if rest:
+            for i, vec in zip(rest, extract_fields_host(self.holder, index, [fields[i] for i in rest], cols)):
+                data[i] = vec
+        return ExtractedTable(names, cols, data)
 
     def hbm_bytes(self) -> int:
         with self.mu:

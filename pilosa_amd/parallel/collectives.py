@@ -710,6 +710,10 @@ TAG_GROUPS_SUM = 11
 # Distinct()'s SignedRow: [tag] then pos and neg one after the other, each as
 # TAG_ROW's body [segments, (shard, bytes) per segment, the segments' words]
 TAG_SIGNED_ROW = 12
+# Extract()'s ExtractedTable (untranslated): [tag, fields F, columns n, bytes of
+# the JSON [[name, type], ...]] + those bytes + columns[n] + per field (values[n],
+# valid[n]) for a scalar type, (offsets[n + 1], rows[offsets[n]]) for a list type
+TAG_EXTRACT = 13
 
 
 def encode_row_block(blk, device):
@@ -747,9 +751,22 @@ def _words_to_bytes(w: np.ndarray, n: int) -> bytes:
 
 def encode_partial(obj) -> np.ndarray:
     """One rank's partial result -> int64[...] (see the TAG_ layout)."""
-    from pilosa_amd.executor import GroupCount, RowIdentifiers, SignedRow, ValCount
+    from pilosa_amd.executor import ExtractedTable, GroupCount, RowIdentifiers, SignedRow, ValCount
     from pilosa_amd.models.cache import Pair, PairArray
     from pilosa_amd.models.row import Row
+
+    if isinstance(obj, ExtractedTable) and obj.keys is None:
+        import json
+        names = json.dumps(obj.fields).encode()
+        segs = [np.array([TAG_EXTRACT, len(obj.fields), len(obj.columns), len(names)], np.int64),
+                _bytes_to_words(names), obj.columns.view(np.int64)]
+        for (_, t), (a, b) in zip(obj.fields, obj.data):
+            if ExtractedTable.is_list(t):
+                segs += [a.astype(np.int64), np.ascontiguousarray(b, dtype=np.uint64).view(np.int64)]
+            else:
+                a = np.ascontiguousarray(a)
+                segs += [a.view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64), b.astype(np.int64)]
+        return np.concatenate(segs)
 
     def msg():
         b = encode(obj)
@@ -812,7 +829,7 @@ def encode_partial(obj) -> np.ndarray:
 def decode_partial(w: np.ndarray):
     """Inverse of :func:`encode_partial`."""
     from pilosa_amd import _roaring
-    from pilosa_amd.executor import FieldRow, GroupCount, RowIdentifiers, SignedRow, ValCount
+    from pilosa_amd.executor import ExtractedTable, FieldRow, GroupCount, RowIdentifiers, SignedRow, ValCount
     from pilosa_amd.models.cache import Pair
     from pilosa_amd.models.row import Row
 
@@ -887,6 +904,31 @@ def decode_partial(w: np.ndarray):
 
     if tag == TAG_ROW:
         return row_body(1)[0]
+    if tag == TAG_EXTRACT:
+        import json
+        nf, n, nb = int(w[1]), int(w[2]), int(w[3])
+        fields = [tuple(x) for x in json.loads(_words_to_bytes(w[4:4 + (nb + 7) // 8], nb).decode())]
+        o = 4 + (nb + 7) // 8
+        cols = w[o:o + n].view(np.uint64).copy()
+        o += n
+        data = []
+        for _, t in fields:
+            if ExtractedTable.is_list(t):
+                offs = w[o:o + n + 1].copy()
+                o += n + 1
+                m = int(offs[-1])
+                data.append((offs, w[o:o + m].view(np.uint64).copy()))
+                o += m
+            else:
+                vals = w[o:o + n]
+                if t == "uint64":
+                    vals = vals.view(np.uint64).copy()
+                else:
+                    vals = vals.astype(np.bool_ if t == "bool" else np.int64)
+                data.append((vals, w[o + n:o + 2 * n].astype(bool)))
+                o += 2 * n
+        assert len(fields) == nf
+        return ExtractedTable(fields, cols, data)
     if tag == TAG_SIGNED_ROW:
         pos, o = row_body(1)
         return SignedRow(pos, row_body(o)[0])

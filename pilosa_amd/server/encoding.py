@@ -4,11 +4,13 @@ from __future__ import annotations
 
 from typing import Any, List, Optional
 
-from pilosa_amd.executor import FieldRow, GroupCount, QueryResponse, RowIdentifiers, SignedRow, ValCount
+from pilosa_amd.executor import (ExtractedTable, FieldRow, GroupCount, QueryResponse, RowIdentifiers, SignedRow,
+                                 ValCount)
 from pilosa_amd.models.cache import Pair, PairArray
 from pilosa_amd.models.row import Row
 from pilosa_amd.wire import (ATTR_TYPE_BOOL, ATTR_TYPE_FLOAT, ATTR_TYPE_INT, ATTR_TYPE_STRING,
-                             QUERY_RESULT_TYPE_BOOL, QUERY_RESULT_TYPE_GROUPCOUNTS, QUERY_RESULT_TYPE_NIL,
+                             QUERY_RESULT_TYPE_BOOL, QUERY_RESULT_TYPE_EXTRACTEDTABLE, QUERY_RESULT_TYPE_GROUPCOUNTS,
+                             QUERY_RESULT_TYPE_NIL,
                              QUERY_RESULT_TYPE_PAIR, QUERY_RESULT_TYPE_PAIRS, QUERY_RESULT_TYPE_ROW,
                              QUERY_RESULT_TYPE_ROWIDENTIFIERS, QUERY_RESULT_TYPE_ROWIDS, QUERY_RESULT_TYPE_SIGNEDROW,
                              QUERY_RESULT_TYPE_UINT64, QUERY_RESULT_TYPE_VALCOUNT, pb)
@@ -21,7 +23,8 @@ def result_to_json(r: Any):
         return r
     if isinstance(r, int):
         return r
-    if isinstance(r, (Row, ValCount, Pair, RowIdentifiers, GroupCount, FieldRow, PairArray, SignedRow)):
+    if isinstance(r, (Row, ValCount, Pair, RowIdentifiers, GroupCount, FieldRow, PairArray, SignedRow,
+                      ExtractedTable)):
         return r.to_json()
     if isinstance(r, list):
         return [result_to_json(x) for x in r]
@@ -89,6 +92,53 @@ def attrs_from_pb(attrs) -> dict:
     return d
 
 
+def extracted_to_pb(r: ExtractedTable, t) -> None:
+    """Column-major: whole arrays go into packed repeated fields, never one
+    message (or one Python step) per cell."""
+    import numpy as np
+    t.Columns.extend(r.columns.tolist())
+    if r.keys is not None:
+        t.Keys.extend(r.keys)
+    for (name, typ), (a, b) in zip(r.fields, r.data):
+        f = t.Fields.add(Name=name, Type=typ)
+        if ExtractedTable.is_list(typ):
+            f.Offsets.extend(a.tolist())
+            if typ == "[]string":
+                f.StringKeys.extend(b)
+            else:
+                f.Rows.extend(b.tolist())
+            continue
+        f.Valid = np.packbits(b, bitorder="little").tobytes()
+        if typ == "string":
+            f.StringKeys.extend(a)
+        elif typ == "uint64":
+            f.Rows.extend(a.tolist())
+        else:
+            f.Values.extend(a.astype(np.int64).tolist())
+
+
+def extracted_from_pb(t) -> ExtractedTable:
+    import numpy as np
+    cols = np.array(t.Columns, dtype=np.uint64)
+    n = len(cols)
+    fields, data = [], []
+    for f in t.Fields:
+        fields.append((f.Name, f.Type))
+        if ExtractedTable.is_list(f.Type):
+            offs = np.array(f.Offsets, dtype=np.int64) if len(f.Offsets) else np.zeros(n + 1, np.int64)
+            data.append((offs, list(f.StringKeys) if f.Type == "[]string" else np.array(f.Rows, dtype=np.uint64)))
+            continue
+        valid = np.unpackbits(np.frombuffer(f.Valid, np.uint8), bitorder="little")[:n].astype(bool)
+        if f.Type == "string":
+            vals = list(f.StringKeys)
+        elif f.Type == "uint64":
+            vals = np.array(f.Rows, dtype=np.uint64)
+        else:
+            vals = np.array(f.Values, dtype=np.int64).astype(np.bool_ if f.Type == "bool" else np.int64)
+        data.append((vals, valid))
+    return ExtractedTable(fields, cols, data, list(t.Keys) if len(t.Keys) else None)
+
+
 def result_to_pb(r: Any, call_name: str = ""):
     m = pb.QueryResult()
     if r is None:
@@ -112,6 +162,9 @@ def result_to_pb(r: Any, call_name: str = ""):
         m.Type = QUERY_RESULT_TYPE_SIGNEDROW
         m.SignedRow.Neg.Columns.extend(int(c) for c in r.neg.columns())
         m.SignedRow.Pos.Columns.extend(int(c) for c in r.pos.columns())
+    elif isinstance(r, ExtractedTable):
+        m.Type = QUERY_RESULT_TYPE_EXTRACTEDTABLE
+        extracted_to_pb(r, m.ExtractedTable)
     elif isinstance(r, Pair):
         m.Type = QUERY_RESULT_TYPE_PAIR
         m.Pairs.add(ID=r.id, Key=r.key, Count=r.count)
@@ -166,6 +219,8 @@ def result_from_pb(m):
         import numpy as np
         return SignedRow(Row(np.array(list(m.SignedRow.Pos.Columns), dtype=np.uint64)),
                          Row(np.array(list(m.SignedRow.Neg.Columns), dtype=np.uint64)))
+    if t == QUERY_RESULT_TYPE_EXTRACTEDTABLE:
+        return extracted_from_pb(m.ExtractedTable)
     if t == QUERY_RESULT_TYPE_PAIR:
         p = m.Pairs[0]
         return Pair(p.ID, p.Count, p.Key)

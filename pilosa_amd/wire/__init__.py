@@ -89,6 +89,7 @@ QUERY_RESULT_TYPE_GROUPCOUNTS = 7
 QUERY_RESULT_TYPE_ROWIDENTIFIERS = 8
 QUERY_RESULT_TYPE_PAIR = 9
 QUERY_RESULT_TYPE_SIGNEDROW = 10   # pilosa_amd extension (Distinct)
+QUERY_RESULT_TYPE_EXTRACTEDTABLE = 11   # pilosa_amd extension (Extract)
 
 # Attr.Type codes
 ATTR_TYPE_STRING = 1
