@@ -51,8 +51,9 @@ _PERCENTILE_DEVICE_DEFAULT = "1"
 # Distinct(): the device pass (GpuExecutor.bsi_distinct) against the host gather;
 # the default follows the measurement in profiles/distinct/README.md
 _DISTINCT_DEVICE_DEFAULT = "1"
-# Extract(): the device route for int fields (GpuExecutor.bsi_extract) against
-# the host gather; the default follows profiles/extract/README.md
+# Extract(): the device route (GpuExecutor.bsi_extract) against the host
+# gather; the default follows profiles/extract/README.md (set-like fields have
+# a switch of their own, ops/gpu_executor.py EXTRACT_ROWS_DEVICE_DEFAULT)
 _EXTRACT_DEVICE_DEFAULT = "1"
 
 
@@ -1794,7 +1795,8 @@ class Executor:
         The map step returns a shard's table cut to its first offset + limit
         columns (Fragment.extract_values / extract_rows on the host; on the
         device the int fields of all local shards in one bsi_extract_kernel
-        pass each, GpuExecutor.bsi_extract).  The reduce step concatenates in
+        pass each and the set-like fields through rows_extract_kernel,
+        GpuExecutor.bsi_extract).  The reduce step concatenates in
         column order and keeps the first offset + limit.  Only the
         coordinating node applies ``offset``: a node answering a remote or
         mesh request returns its first offset + limit columns.

@@ -374,6 +374,62 @@ int64_t bsi_extract(torch::Tensor progs, torch::Tensor views, int64_t S, torch::
   return n;
 }
 
+// Extract of a set-like field (rows_extract_kernel, see kernels.h): mode 1 counts into wg[blocks] (zeroed by the
+// caller), mode 2 fills keys[T] behind the bases wg[blocks], mode 3 takes the minimum row id per position into
+// first[>= cap]; D = the rows of views[fview]; columns may be empty (not written).  Returns the workgroups run.
+int64_t rows_extract(int64_t mode, torch::Tensor progs, torch::Tensor views, int64_t S, int64_t fview, int64_t D,
+                     int64_t rows_per_block, int64_t rows_per_wave, torch::Tensor unit_off, torch::Tensor col_base,
+                     int64_t cap, torch::Tensor columns, torch::Tensor wg, torch::Tensor keys, torch::Tensor row_ids,
+                     torch::Tensor first) {
+  check_dev(progs, "progs");
+  check_dev(views, "views");
+  check_dev(unit_off, "unit_off");
+  check_dev(col_base, "col_base");
+  TORCH_CHECK(mode >= 1 && mode <= 3, "rows_extract: mode 1 (count), 2 (fill) or 3 (scalar)");
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24) && D >= 0 && rows_per_block >= 0 && cap >= 0, "rows_extract sizes");
+  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  TORCH_CHECK(fview >= 0 && fview < views.numel() / int64_t(sizeof(pk::ViewDev)), "rows_extract: view slot");
+  TORCH_CHECK(unit_off.scalar_type() == torch::kInt64 && unit_off.numel() >= S * 16, "unit_off must be int64[S * 16]");
+  TORCH_CHECK(col_base.scalar_type() == torch::kInt64 && col_base.numel() >= S, "col_base must be int64[S]");
+  const int64_t blocks = pk::rows_extract_blocks(int(S), D, rows_per_block);
+  TORCH_CHECK(blocks >= 0, "rows_extract: grid too large");
+  uint64_t* cols = nullptr;
+  if (columns.numel()) {
+    check_dev(columns, "columns");
+    TORCH_CHECK(columns.scalar_type() == torch::kInt64 && columns.numel() >= cap, "columns must be int64[>= cap]");
+    cols = reinterpret_cast<uint64_t*>(columns.data_ptr<int64_t>());
+  }
+  int64_t *wgp = nullptr, *keyp = nullptr, *firstp = nullptr, *rowp = nullptr;
+  int64_t T = 0;
+  if (mode == 3) {
+    check_dev(row_ids, "row_ids");
+    check_dev(first, "first");
+    TORCH_CHECK(row_ids.scalar_type() == torch::kInt64 && row_ids.numel() >= D, "row_ids must be int64[D]");
+    TORCH_CHECK(first.scalar_type() == torch::kInt64 && first.numel() >= cap, "first must be int64[>= cap]");
+    rowp = row_ids.data_ptr<int64_t>();
+    firstp = first.data_ptr<int64_t>();
+  } else {
+    check_dev(wg, "wg");
+    TORCH_CHECK(wg.scalar_type() == torch::kInt64 && wg.numel() >= blocks, "wg must be int64[blocks]");
+    wgp = wg.data_ptr<int64_t>();
+    if (mode == 2) {
+      check_dev(keys, "keys");
+      TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64[T]");
+      keyp = keys.data_ptr<int64_t>();
+      T = keys.numel();
+    }
+  }
+  const int64_t n = pk::launch_rows_extract(
+      int(mode), reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
+      reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), int(fview), D, rows_per_block,
+      int(rows_per_wave < 0 || rows_per_wave > 64 ? 0 : rows_per_wave), unit_off.data_ptr<int64_t>(),
+      col_base.data_ptr<int64_t>(), cap, cols, wgp, keyp, T, reinterpret_cast<const uint64_t*>(rowp),
+      reinterpret_cast<uint64_t*>(firstp), cur_stream(views));
+  TORCH_CHECK(n >= 0, "rows_extract: not launched");
+  check_launch("rows_extract");
+  return n;
+}
+
 void bsi_minmax_fold(torch::Tensor o, int64_t F, int64_t G, int64_t is_min, torch::Tensor out) {
   check_dev(o, "o");
   check_dev(out, "out");
@@ -1314,6 +1370,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("src"), py::arg("S"), py::arg("n"), py::arg("main_out"), py::arg("main_meta"), py::arg("spill_out"),
         py::arg("spill_meta"), py::arg("M") = 1, py::arg("row_words") = 16384);
   m.def("rows_list", &rows_list, "flag dense rows with non-empty containers (optionally holding one column)");
+  m.def("rows_extract", &rows_extract,
+        "Extract: the rows of a set-like field per filter column (count / fill / scalar)");
+  m.def("rows_extract_blocks",
+        [](int64_t S, int64_t D, int64_t rows_per_block) { return pk::rows_extract_blocks(int(S), D, rows_per_block); },
+        "Extract: workgroups of a rows_extract launch (-1: the grid would not fit)");
   m.def("row_filter_counts", &row_filter_counts,
         "TopK: per-row intersection counts of a whole field with one LDS-staged filter row", py::arg("view"),
         py::arg("filter"), py::arg("filter_row"), py::arg("S"), py::arg("out"), py::arg("rows_per_block") = 0,

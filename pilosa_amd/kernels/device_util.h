@@ -21,6 +21,17 @@ extern "C" __device__ long __ockl_wfred_add_i64(long);
 __device__ __forceinline__ int wave_sum(int v) { return __ockl_wfred_add_i32(v); }
 __device__ __forceinline__ int64_t wave_sum_i64(int64_t v) { return int64_t(__ockl_wfred_add_i64(long(v))); }
 
+// inclusive prefix sum over the wave's 64 lanes (all lanes active)
+__device__ __forceinline__ int wave_scan_incl(int v) {
+  const int lane = wave_lane();
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d, 64);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+
 // broadcast lane `src` (wave-uniform) with scalar readlanes, no LDS pipe
 __device__ __forceinline__ uint64_t rl_u64(uint64_t v, int src) {
   return (uint64_t(uint32_t(__builtin_amdgcn_readlane(int(v >> 32), src))) << 32) |

@@ -66,17 +66,6 @@
 
 namespace pk {
 
-// inclusive prefix sum over the wave's 64 lanes (all lanes active)
-__device__ __forceinline__ int wave_scan_incl(int v) {
-  const int lane = wave_lane();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d, 64);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(256) void bsi_extract_kernel(const QueryProg* __restrict__ progs,
                                                           const ViewDev* __restrict__ views, int S, BsiArgs bsi, int n,
                                                           const int64_t* __restrict__ unit_off,

@@ -176,6 +176,25 @@ int launch_bsi_extract(const QueryProg* progs, const ViewDev* views, int S, BsiA
                        const int64_t* unit_off, const int64_t* col_base, int64_t base, int64_t cap, uint64_t* columns,
                        int64_t* values, uint8_t* valid, hipStream_t st);
 
+// Extract(filter, Rows(field=)) for a set-like field (extract_rows_kernels.hip,
+// K28): every hit of a dense row d < D of views[fview] on the filter progs[0]
+// at an output position pos < cap (unit_off / col_base / the positions as for
+// launch_bsi_extract; cap = the window's length).  One workgroup per (shard,
+// key, chunk of rows_per_block rows; 0 = all rows), rows_per_wave as for
+// launch_row_filter_counts; rows_extract_blocks() is the grid, which the two
+// list passes must share.  mode 1 (count): wg[block] = the workgroup's hits
+// (zeroed by the caller).  mode 2 (fill): wg = the exclusive cumsum of the
+// counts, keys[base + slot] = pos * D + d, no store at or past T.  mode 3
+// (scalar): first[pos] = min(first[pos], row_ids[d]), first[cap] initialised
+// to all ones.  columns != nullptr: the launch also writes the column vector
+// (>= cap entries).  Returns the workgroups launched, -1 when nothing was
+// launched (grid too large, bad mode).
+int64_t rows_extract_blocks(int S, int64_t D, int64_t rows_per_block);
+int64_t launch_rows_extract(int mode, const QueryProg* progs, const ViewDev* views, int S, int fview, int64_t D,
+                            int64_t rows_per_block, int rows_per_wave, const int64_t* unit_off,
+                            const int64_t* col_base, int64_t cap, uint64_t* columns, int64_t* wg, int64_t* keys,
+                            int64_t T, const uint64_t* row_ids, uint64_t* first, hipStream_t st);
+
 // TopK(field=, k=) (topk_kernels.hip, K25): out[d] +=|row d ∩ filter| over
 // the S arena shards for every dense row d of ``fv``; the filter is dense row
 // ``xd`` of ``*xv`` (same shard list), staged once per (shard, key) in LDS.

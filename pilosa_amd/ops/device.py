@@ -2121,11 +2121,25 @@ class GpuEngine:
     # bit planes bsi_extract_kernel transposes at most (kernels.h EXTRACT_MAX_PLANES)
     EXTRACT_MAX_PLANES = 32
 
+    # rows_extract_kernel (K28): dense rows of a (shard, key) per workgroup (0 =
+    # all of them) and the most (column, row) entries one list field may hold
+    # on the device -- 8 B per key plus the sort's temporaries, a memory choice,
+    # not a measured optimum
+    EXTRACT_ROWS_PER_BLOCK = 2048
+    EXTRACT_ROWS_MAX_ENTRIES = 1 << 26
+
     def bsi_extract(self, filt: object, fields: Sequence[Tuple["DeviceView", int, int]], window: Optional[int] = None,
-                    slots: int = 0, guard=None):
+                    slots: int = 0, guard=None, rows: Sequence[Tuple["DeviceView", str]] = ()):
         """The columns of ``filt`` over the local shards, ascending, and their
-        values in the BSI ``fields`` [(view, depth, base)]: (uint64 columns,
-        [(int64 values, bool validity) per field], the filter's count).
+        values in the BSI ``fields`` [(view, depth, base)] and the set-like
+        fields ``rows`` [(standard view, type)], type "[]uint64" (set, time),
+        "uint64" (mutex) or "bool": (uint64 columns, [one vector per field,
+        ``fields`` first, then ``rows``], the filter's count).  A BSI vector is
+        (int64 values, bool validity), a scalar set-like one (values,
+        validity), a list one the CSR (int64 offsets, uint64 rows) of
+        Fragment.extract_rows -- or None where the field has to be answered
+        by the host: more than PILOSA_EXTRACT_ROWS_MAX_ENTRIES entries, or
+        keys that would not fit 63 bits.
 
         1. one expr_count launch of the filter program: int32 counts per
            (shard, key);
@@ -2135,22 +2149,32 @@ class GpuEngine:
            one transfer, and ``guard(total)`` (the size guard) runs when there
            is no window; units that are empty or start beyond the window get
            offset -1;
-        3. one bsi_extract_kernel launch per field; they share the offsets, and
-           only the first writes the column vector.  The vectors are cut to
-           the window and copied to the host, one transfer each.
+        3. one bsi_extract_kernel launch per BSI field, then the
+           rows_extract_kernel launches of the set-like fields (one for a
+           scalar field; a count pass, a cumsum whose total is read in one
+           transfer, a fill pass and a torch.sort for a list field).  All
+           share the offsets, and only the first launch writes the column
+           vector.  The vectors are cut to the window and copied to the host.
 
-        The output vectors are (8 + 9 * fields) bytes per column from torch's
-        caching allocator, per request, outside the arenas' ``hbm_budget``."""
+        The output vectors are (8 + 9 * BSI fields + 8 * scalar fields) bytes
+        per column plus 8 bytes per workgroup and 16 bytes per entry of a list
+        field next to the sort's temporaries, from torch's caching allocator,
+        per request, outside the arenas' ``hbm_budget``."""
         torch = self.torch
         from pilosa_amd import shardwidth
-        bv0 = fields[0][0]
+        bv0 = fields[0][0] if fields else rows[0][0]
         S = bv0.S
         for bv, depth, _ in fields:
             if depth < 0 or depth > self.EXTRACT_MAX_PLANES:
                 raise NotImplementedError("bit depth beyond the transpose")
             if bv.S != S:
                 raise NotImplementedError("views over different shards")
-        none = (np.zeros(0, np.uint64), [(np.zeros(0, np.int64), np.zeros(0, bool)) for _ in fields], 0)
+        for rv, _ in rows:
+            if rv.S != S or tuple(rv.shards) != tuple(bv0.shards):
+                raise NotImplementedError("views over different shards")
+        from pilosa_amd.executor import ExtractedTable
+        none = (np.zeros(0, np.uint64), [(np.zeros(0, np.int64), np.zeros(0, bool)) for _ in fields] +
+                [ExtractedTable.null_vector(typ, 0) for _, typ in rows], 0)
         if not S:
             return none
         progs, ordered = self._bsi_filter_program(filt, bv0)
@@ -2184,9 +2208,81 @@ class GpuEngine:
             self.ext.bsi_extract(tp, tv, S, torch.from_numpy(self.bsi_args(bv, depth)), int(slots), unit_off, col_base,
                                  int(base), columns if i == 0 else columns[:0], values, valid)
             out.append((values, valid))
+        row_out = [self._rows_extract(filt, rv, typ, unit_off, col_base, keep,
+                                      columns if not fields and i == 0 else columns[:0])
+                   for i, (rv, typ) in enumerate(rows)]
         cols = self.to_host(columns[:keep]).numpy().view(np.uint64)
-        return cols, [(self.to_host(v[:keep]).numpy(), self.to_host(ok[:keep]).numpy().astype(bool))
-                      for v, ok in out], int(total)
+        vecs = [(self.to_host(v[:keep]).numpy(), self.to_host(ok[:keep]).numpy().astype(bool)) for v, ok in out]
+        return cols, vecs + [fin() if fin is not None else None for fin in row_out], int(total)
+
+    # K28 launches so far (GpuExecutor.stats()["extractRowsLaunches"])
+    rows_extract_launches = 0
+
+    def _rows_extract(self, filt: object, view: "DeviceView", typ: str, unit_off, col_base, keep: int, columns):
+        """One set-like field of :meth:`bsi_extract` through rows_extract_kernel
+        (K28): the launches are enqueued here; the returned function copies
+        the field's vector to the host (None: the host has to answer it).
+        ``columns``: the column vector for the first launch to write, or an
+        empty tensor."""
+        torch = self.torch
+        from pilosa_amd.executor import ExtractedTable
+        from pilosa_amd.models.fragment import TRUE_ROW_ID
+        S, D = view.S, view.D
+        view.ensure_keymask()
+        progs, ordered = self._bsi_filter_program(filt, view)   # the field's view in slot 0
+        tp, tv = self.upload_batch(progs, ordered)
+        rpb = max(0, int(os.environ.get("PILOSA_EXTRACT_ROWS_PER_BLOCK") or self.EXTRACT_ROWS_PER_BLOCK))
+        rpw = int(os.environ.get("PILOSA_EXTRACT_ROWS_PER_WAVE") or 0)
+        none64 = torch.empty(0, dtype=torch.int64, device=self.device)
+        rows_t = self._rows_tensor(view)
+
+        def launch(mode, cols, wg, keys, first):
+            self.ext.rows_extract(mode, tp, tv, S, 0, D, rpb, rpw, unit_off, col_base, keep, cols, wg, keys,
+                                  rows_t if mode == 3 else none64, first)
+            self.rows_extract_launches += 1
+
+        if not ExtractedTable.is_list(typ):
+            first = torch.full((keep,), -1, dtype=torch.int64, device=self.device)   # all ones: no row
+            launch(3, columns, none64, none64, first)
+            valid = first != -1
+            value = (first == int(TRUE_ROW_ID)) if typ == "bool" else torch.where(valid, first, torch.zeros_like(first))
+
+            def scalar():
+                v = self.to_host(value).numpy()
+                ok = self.to_host(valid).numpy().astype(bool)
+                return (v.astype(bool) if typ == "bool" else v.view(np.uint64)), ok
+            return scalar
+        if D and keep * D >= 1 << 63:
+            return None
+        blocks = int(self.ext.rows_extract_blocks(S, D, rpb))
+        if blocks < 0:
+            raise NotImplementedError("rows_extract: the grid would not fit")
+        wg = torch.zeros(blocks, dtype=torch.int64, device=self.device)
+        launch(1, columns, wg, none64, none64)
+        wg_end = torch.cumsum(wg, 0)
+        T = int(self.to_host(wg_end[-1:]).item())
+        try:
+            cap_t = int(os.environ.get("PILOSA_EXTRACT_ROWS_MAX_ENTRIES") or self.EXTRACT_ROWS_MAX_ENTRIES)
+        except ValueError:
+            cap_t = self.EXTRACT_ROWS_MAX_ENTRIES
+        if T > cap_t:
+            return None
+        if not T:
+            return lambda: ExtractedTable.null_vector(typ, keep)
+        # -1 = a slot the fill pass did not reach (data that changed between the passes): sorted to the front
+        keys = torch.full((T,), -1, dtype=torch.int64, device=self.device)
+        launch(2, none64, (wg_end - wg).contiguous(), keys, none64)
+        keys = torch.sort(keys).values       # ascending by column, then by dense row = by row id
+        pos = torch.where(keys < 0, torch.full_like(keys, keep), torch.div(keys, D, rounding_mode="floor"))
+        offsets = torch.zeros(keep + 1, dtype=torch.int64, device=self.device)
+        offsets[1:] = torch.cumsum(torch.bincount(pos, minlength=keep + 1)[:keep], 0)
+        row_ids = rows_t[torch.remainder(keys.clamp(min=0), D)]
+
+        def csr():
+            o = self.to_host(offsets).numpy()
+            r = self.to_host(row_ids).numpy().view(np.uint64)
+            return o, r[len(r) - int(o[-1]):]
+        return csr
 
     def _bsi_minmax_dev(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, which: str = ""):
         torch = self.torch

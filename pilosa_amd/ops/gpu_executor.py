@@ -16,6 +16,8 @@ device arenas of the involved field-views:
 * ``bsi_extract`` Extract(<filter>, Rows(field=f)...) -> expr_count (offsets per
                 (shard, key)) + one bsi_extract_kernel pass per int field
                 (planes staged, transposed, written compacted in column order)
+                and rows_extract_kernel for set, time, mutex and bool fields
+                (filter tile and rank table staged, every row streamed past)
 * ``topk``      TopK(<filter>, field=f, k=n)           -> row_filter_counts (one
                 pass: filter staged per (shard, key), every row streamed past)
 * ``topn``      TopN phase-1/phase-2 with src          -> slot-index LDS
@@ -118,6 +120,19 @@ def extract_slots_env() -> int:
     except ValueError:
         return EXTRACT_SLOTS_DEFAULT
     return v if v in (1, 2, 4, 8) else EXTRACT_SLOTS_DEFAULT
+
+
+# Extract(): set, time, mutex and bool fields through rows_extract_kernel (K28)
+# when PILOSA_EXTRACT_ROWS_DEVICE is unset; the default follows
+# profiles/extract_rows/README.md
+EXTRACT_ROWS_DEVICE_DEFAULT = "1"
+
+
+def extract_rows_device() -> bool:
+    """PILOSA_EXTRACT_ROWS_DEVICE: 0 keeps the set-like fields of Extract() on
+    the host (int fields are not affected), 1 sends them to rows_extract_kernel;
+    unset means EXTRACT_ROWS_DEVICE_DEFAULT."""
+    return os.environ.get("PILOSA_EXTRACT_ROWS_DEVICE", EXTRACT_ROWS_DEVICE_DEFAULT) not in ("0", "")
 
 
 class _Empty:
@@ -239,6 +254,7 @@ class GpuExecutor:
         self.percentile_device = 0       # Percentile() calls answered by bsi_percentile (the fast path)
         self.distinct_device = 0         # Distinct() map steps answered by bsi_distinct (K26)
         self.extract_device = 0          # Extract() (map step, int field) pairs answered by bsi_extract (K27)
+        self.extract_rows_device = 0     # ... (map step, set-like field) pairs answered by rows_extract (K28)
         self.topk_device = 0             # TopK() map steps answered by row_filter_counts_kernel
         self.topk_programs = 0           # ... and by the per-row programs route
         # serving Count text path: host prep (parse..launch) vs result wait
@@ -461,7 +477,8 @@ class GpuExecutor:
                 "rowUpdates": self.row_updates, "deviceWrites": self.device_writes,
                 "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
                 "percentileDevice": self.percentile_device, "distinctDevice": self.distinct_device,
-                "extractDevice": self.extract_device,
+                "extractDevice": self.extract_device, "extractRowsDevice": self.extract_rows_device,
+                "extractRowsLaunches": self.engine.rows_extract_launches,
                 "groupSumDevice": self.group_sum_device,
                 "groupSumPerFilter": self.group_sum_per_filter, "topkDevice": self.topk_device,
                 "topkPrograms": self.topk_programs}
@@ -739,38 +756,53 @@ class GpuExecutor:
         """Extract(<filter>, Rows(field=)...) over the local shards -> ONE
         ExtractedTable of the filter's first ``window`` columns (None: all).
         Routing is per field: an int field of depth <= 32 is answered by
-        bsi_extract_kernel (GpuEngine.bsi_extract: a count pass, a cumsum, one
-        launch per field); every other field -- set, time, mutex, bool, a
-        deeper int field -- by the host function over the device's column
-        vector.  No int field the kernel can take, a filter the planner cannot
-        take or a CompileError leave the whole map step to the host.
-        PILOSA_EXTRACT_SLOTS sets the tile slots per workgroup."""
+        bsi_extract_kernel (K27), a set, time, mutex or bool field whose
+        standard view has an arena by rows_extract_kernel (K28: the list modes
+        for set and time -- the standard view only, as on the host --, the
+        scalar mode for mutex and bool) while PILOSA_EXTRACT_ROWS_DEVICE
+        allows it; both inside GpuEngine.bsi_extract, which runs the count
+        pass and the cumsum once for all of them.  Every other field -- a
+        deeper int field, a field without an arena, a list field of more than
+        PILOSA_EXTRACT_ROWS_MAX_ENTRIES entries -- is answered by the host
+        function over the device's column vector.  No field the device can
+        take, a filter the planner cannot take or a CompileError leave the
+        whole map step to the host.  PILOSA_EXTRACT_SLOTS sets K27's tile slots
+        per workgroup, PILOSA_EXTRACT_ROWS_PER_BLOCK / _PER_WAVE K28's rows per
+        workgroup and per wave step."""
         from pilosa_amd.executor import (ExtractedTable, extract_field_type, extract_fields_host, extract_guard)
         from pilosa_amd.models.field import FIELD_TYPE_INT
         names = [(f.name, extract_field_type(f)) for f in fields]
-        dev = []
+        dev, rdev = [], []
+        rows_ok = extract_rows_device()
         for i, f in enumerate(fields):
-            b = f.bsi_group(f.name) if f.type == FIELD_TYPE_INT else None
-            if b is not None and b.bit_depth <= GpuEngine.EXTRACT_MAX_PLANES:
-                bv = self.view_arena(index, f.name, VIEW_BSI_PREFIX + f.name, shards)
-                if bv is not None:
-                    dev.append((i, bv, b.bit_depth, b.base))
-        if not dev:
+            if f.type == FIELD_TYPE_INT:
+                b = f.bsi_group(f.name)
+                if b is not None and b.bit_depth <= GpuEngine.EXTRACT_MAX_PLANES:
+                    bv = self.view_arena(index, f.name, VIEW_BSI_PREFIX + f.name, shards)
+                    if bv is not None:
+                        dev.append((i, bv, b.bit_depth, b.base))
+            elif rows_ok:
+                rv = self.view_arena(index, f.name, VIEW_STANDARD, shards)
+                if rv is not None:
+                    rdev.append((i, rv, names[i][1]))
+        if not dev and not rdev:
             raise NotImplementedError
         filt = self.plan(index, filt_call, shards)
         if filt is EMPTY:
             self.extract_device += len(dev)   # a filter known empty from the schema: no launch
+            self.extract_rows_device += len(rdev)
             return ExtractedTable(names)
         try:
             cols, vecs, _ = self.engine.bsi_extract(filt, [d[1:] for d in dev], window, extract_slots_env(),
-                                                    extract_guard)
+                                                    extract_guard, rows=[r[1:] for r in rdev])
         except CompileError:
             raise NotImplementedError
         self.extract_device += len(dev)
         self.launches += 1 + len(dev)
         data = [None] * len(fields)
-        for (i, *_), vec in zip(dev, vecs):
+        for (i, *_), vec in zip(dev + rdev, vecs):
             data[i] = vec
+        self.extract_rows_device += sum(1 for i, *_ in rdev if data[i] is not None)
         rest = [i for i in range(len(fields)) if data[i] is None]
         if rest:
             for i, vec in zip(rest, extract_fields_host(self.holder, index, [fields[i] for i in rest], cols)):
