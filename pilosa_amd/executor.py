@@ -55,6 +55,9 @@ _DISTINCT_DEVICE_DEFAULT = "1"
 # gather; the default follows profiles/extract/README.md (set-like fields have
 # a switch of their own, ops/gpu_executor.py EXTRACT_ROWS_DEVICE_DEFAULT)
 _EXTRACT_DEVICE_DEFAULT = "1"
+# Sort(): the device route (GpuExecutor.bsi_sort, K29) against the host gather;
+# the default follows profiles/sort/README.md
+_SORT_DEVICE_DEFAULT = "1"
 
 
 # a request that is one unfiltered BSI aggregate: Sum|Min|Max(field=<name>)
@@ -366,6 +369,66 @@ def extract_fields_host(holder, index: str, fields, cols: np.ndarray) -> list:
     if not parts:
         return ExtractedTable(names).data
     return ExtractedTable.concat(parts).data
+
+
+class SortedColumns:
+    """Sort()'s result: ``columns`` (uint64) and ``values`` (int64, real
+    values, never key-translated), parallel vectors in answer order; ``keys``
+    the columns' string keys on a keyed index, set by the key translation."""
+    __slots__ = ("columns", "values", "keys")
+
+    def __init__(self, columns=None, values=None, keys: Optional[List[str]] = None):
+        self.columns = np.zeros(0, np.uint64) if columns is None else np.asarray(columns, dtype=np.uint64)
+        self.values = np.zeros(0, np.int64) if values is None else np.asarray(values, dtype=np.int64)
+        self.keys = keys
+
+    def __len__(self):
+        return len(self.columns)
+
+    def slice(self, lo: int, hi: Optional[int] = None) -> "SortedColumns":
+        """Entries [lo, hi) by position (untranslated results only)."""
+        return SortedColumns(self.columns[lo:hi], self.values[lo:hi])
+
+    def merge(self, o: "SortedColumns", window: Optional[int], desc: bool) -> "SortedColumns":
+        """Both in (value, column) order -- descending values with ``desc``,
+        columns ascending either way --, cut to the first ``window``."""
+        cols = np.concatenate([self.columns, o.columns])
+        vals = np.concatenate([self.values, o.values])
+        order = np.lexsort((cols, ~vals if desc else vals))   # ~v = -v - 1: descending, no overflow
+        if window is not None:
+            order = order[:window]
+        return SortedColumns(cols[order], vals[order])
+
+    def to_json(self):
+        return {"keys" if self.keys is not None else "columns": self.keys if self.keys is not None
+                else self.columns.tolist(), "values": self.values.tolist()}
+
+    def __eq__(self, o):
+        return isinstance(o, SortedColumns) and self.keys == o.keys and \
+            np.array_equal(self.columns, o.columns) and np.array_equal(self.values, o.values)
+
+    def __repr__(self):
+        return f"SortedColumns(columns={len(self.columns)})"
+
+
+def _sort_max_columns() -> int:
+    """PILOSA_SORT_MAX_COLUMNS: the most entries one Sort() gathers (default
+    2^20: a memory choice like Extract()'s, not a measured optimum)."""
+    try:
+        v = int(os.environ.get("PILOSA_SORT_MAX_COLUMNS", "") or (1 << 20))
+    except ValueError:
+        return 1 << 20
+    return v if v >= 0 else 1 << 20
+
+
+def sort_guard(n: int):
+    cap = _sort_max_columns()
+    if n > cap:
+        raise PilosaError(f"Sort(): {n} columns exceed the limit of {cap}; page with limit= and offset=")
+
+
+def _sort_device() -> bool:
+    return os.environ.get("PILOSA_SORT_DEVICE", _SORT_DEVICE_DEFAULT) not in ("0", "")
 
 
 class RowIdentifiers:
@@ -987,6 +1050,8 @@ class Executor:
                 return self._distinct(index, c, shards, opt)
             if n == "Extract":
                 return self._extract(index, c, shards, opt)
+            if n == "Sort":
+                return self._sort(index, c, shards, opt)
             if n == "MinRow":
                 return self._minmax_row(index, c, shards, opt, True)
             if n == "MaxRow":
@@ -1855,6 +1920,121 @@ class Executor:
         r = r.slice(0, window)
         return r if opt.remote else r.slice(offset)
 
+    # ================================================================ Sort
+    def sort_params(self, index: str, c: Call):
+        """Sort()'s argument checks -> (field name, its BSI group, offset,
+        limit or None, descending)."""
+        for k in c.args:
+            if k not in ("field", "limit", "offset", "sort-desc"):
+                raise PilosaError(f'Sort(): unknown argument "{k}"')
+        fname = c.args.get("field")
+        if not fname or not isinstance(fname, str):
+            raise PilosaError("Sort(): field required")
+        nums = {}
+        for k in ("limit", "offset"):
+            v = c.args.get(k)
+            if k in c.args and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+                raise PilosaError(f"Sort(): {k} must be a non-negative integer")
+            nums[k] = v
+        desc = c.args.get("sort-desc", False)
+        if not isinstance(desc, bool):
+            raise PilosaError("Sort(): sort-desc must be a boolean")
+        if len(c.children) > 1:
+            raise PilosaError("Sort() only accepts a single bitmap input")
+        f = self.holder.field(index, fname)
+        if f is None:
+            raise ErrFieldNotFound
+        b = f.bsi_group(fname)
+        if f.type != FIELD_TYPE_INT or b is None:
+            raise PilosaError(f'cannot compute Sort() on non-integer field: "{fname}"')
+        return fname, b, nums["offset"] or 0, nums["limit"], desc
+
+    def _sort(self, index: str, c: Call, shards, opt) -> SortedColumns:
+        """Sort(field=<int field>, [limit=], [offset=], [sort-desc=]) and
+        Sort(<one bitmap call>, field=, ...): columns ordered by an int field
+        (Pilosa added the call after v1.3; here an extension).
+
+        The considered columns are those with a value in the field intersected
+        with the filter child (the ``exists & filter`` of Sum, Percentile and
+        Distinct).  They are ordered by real value, ascending or -- with
+        sort-desc=true -- descending, ties by column id ascending in both
+        directions; ``offset`` drops the first, ``limit`` keeps at most that
+        many of the rest.  The answer is a SortedColumns; no considered
+        column, a missing view or fragment, or an empty filter give an empty
+        one.
+
+        The map step returns a shard's first offset + limit entries
+        (Fragment.sort_values on the host; on the device the selection of all
+        local shards in two bsi_sort_select_kernel passes,
+        GpuExecutor.bsi_sort).  The reduce step merges two partials in (value,
+        column) order and keeps the first offset + limit.  Only the
+        coordinating node applies ``offset``: a node answering a remote or
+        mesh request returns its first offset + limit entries.
+
+        The size guard (PILOSA_SORT_MAX_COLUMNS) runs before anything is
+        gathered: on the window when ``limit`` is given, else on the count of
+        the considered columns."""
+        fname, b, offset, limit, desc = self.sort_params(index, c)
+        window = None if limit is None else offset + limit
+        use_gpu = self.gpu is not None and _sort_device()
+
+        def count_guard():
+            consider = Call("Row", {fname: Condition(NEQ, None)})
+            if c.children:
+                consider = Call("Intersect", {}, [c.children[0].clone(), consider])
+            sort_guard(int(self._count(index, Call("Count", {}, [consider]), shards, opt)))
+
+        # as for Extract(): where every shard is local to one device, its own
+        # count of the considered set (N of bsi_kth_init) feeds the guard
+        device_guards = False
+        if window is not None:
+            sort_guard(window)
+        elif not opt.remote:
+            device_guards = use_gpu and bool(shards) and not self._use_mesh(opt) and \
+                not self._has_remote(index, shards, opt)
+            if not device_guards:
+                count_guard()
+
+        def map_fn(shard):
+            frag = self.holder.fragment(index, fname, VIEW_BSI_PREFIX + fname, shard)
+            if frag is None:
+                return SortedColumns()
+            cols, vals = frag.sort_values(self._bsi_filter_shard(index, c, shard), b.bit_depth, window, desc)
+            return SortedColumns(cols, vals + b.base)
+
+        def reduce_fn(p, v):
+            if v is None or not len(v):
+                return v if p is None else p
+            if p is None or not len(p):
+                return v
+            return p.merge(v, window, desc)
+
+        # the coordinating node of a request whose shards are all local to one
+        # device lets the device cut ``offset`` before its one copy to the host
+        alone = not opt.remote and not self.paranoia and not self._use_mesh(opt) and \
+            not self._has_remote(index, shards, opt)
+        cut = []
+
+        def local_fn(ss):
+            try:
+                r = self.gpu.bsi_sort(index, c, fname, b, window, desc, ss, sort_guard, offset if alone else 0)
+                cut.append(alone)
+                return r
+            except PilosaError:
+                raise
+            except Exception:
+                if device_guards:   # the device declined or failed before its guard: the host gather follows
+                    count_guard()
+                raise
+
+        r = self.map_reduce(index, shards, c, opt, map_fn, reduce_fn, local_fn if use_gpu else None)
+        if r is None:
+            r = SortedColumns()
+        if cut == [True]:   # one local map step, already without the first ``offset`` entries
+            return r
+        r = r.slice(0, window)
+        return r if opt.remote else r.slice(offset)
+
     def _minmax_row(self, index: str, c: Call, shards, opt, is_min: bool) -> Pair:
         fname = c.args.get("field")
         if not fname:
@@ -2541,6 +2721,11 @@ class Executor:
                 return r
             keys = ts.translate_columns_to_strings(index, [int(x) for x in r.columns]) if idx.keys else None
             return ExtractedTable(fields, r.columns, data, keys)
+        if isinstance(r, SortedColumns):
+            if idx.keys:
+                return SortedColumns(r.columns, r.values,
+                                     ts.translate_columns_to_strings(index, [int(x) for x in r.columns]))
+            return r
         if isinstance(r, Pair):
             fname = c.args.get("field")
             if isinstance(fname, str) and fname:

@@ -374,6 +374,58 @@ int64_t bsi_extract(torch::Tensor progs, torch::Tensor views, int64_t S, torch::
   return n;
 }
 
+// Sort: the selection pass (bsi_sort_select_kernel, see kernels.h).  mode 1 counts into counts[blocks * 2] (int32,
+// zeroed by the caller); mode 2 fills columns / values[cap] behind before_off / eq_before[blocks] and the tie quota
+// m[1].  Both modes take the same slots; returns the tile slots per workgroup used.
+int64_t bsi_sort_select(int64_t mode, torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor bsi_args,
+                        int64_t slots, bool select_all, bool desc, int64_t T, torch::Tensor counts,
+                        torch::Tensor before_off, torch::Tensor eq_before, torch::Tensor m, torch::Tensor col_base,
+                        int64_t base, torch::Tensor columns, torch::Tensor values) {
+  check_dev(progs, "progs");
+  check_dev(views, "views");
+  TORCH_CHECK(mode == 1 || mode == 2, "bsi_sort_select: mode");
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24), "bsi_sort_select: shard count");
+  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  const pk::BsiArgs b = bsi_args_from(bsi_args);
+  TORCH_CHECK(b.depth >= 0 && b.depth <= pk::SORT_MAX_PLANES, "bsi_sort_select: bit depth");
+  TORCH_CHECK(b.view >= 0 && int64_t(b.view) < views.numel() / int64_t(sizeof(pk::ViewDev)),
+              "bsi_sort_select: view slot");
+  TORCH_CHECK(select_all || (T > -(int64_t(1) << 32) && T < (int64_t(1) << 32)), "bsi_sort_select: threshold");
+  const int64_t blocks = pk::sort_blocks(int(S), pk::sort_slots(b.depth, int(slots)));
+  int32_t* cnt = nullptr;
+  const int64_t *bo = nullptr, *eb = nullptr, *mp = nullptr, *cb = nullptr;
+  int64_t *cols = nullptr, *vals = nullptr, cap = 0;
+  if (mode == 1) {
+    check_dev(counts, "counts");
+    TORCH_CHECK(counts.scalar_type() == torch::kInt32 && counts.is_contiguous() && counts.numel() >= blocks * 2,
+                "counts must be int32[blocks * 2]");
+    cnt = counts.data_ptr<int32_t>();
+  } else {
+    for (const torch::Tensor* t : {&before_off, &eq_before, &m, &col_base, &columns, &values}) {
+      check_dev(*t, "bsi_sort_select tensor");
+      TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->is_contiguous(), "bsi_sort_select: int64 tensors");
+    }
+    TORCH_CHECK(before_off.numel() >= blocks && eq_before.numel() >= blocks, "offsets must be int64[blocks]");
+    TORCH_CHECK(m.numel() >= 1, "m must be int64[1]");
+    TORCH_CHECK(col_base.numel() >= S, "col_base must be int64[S]");
+    cap = values.numel();
+    TORCH_CHECK(columns.numel() == cap, "columns and values must have the same length");
+    bo = before_off.data_ptr<int64_t>();
+    eb = eq_before.data_ptr<int64_t>();
+    mp = m.data_ptr<int64_t>();
+    cb = col_base.data_ptr<int64_t>();
+    cols = columns.data_ptr<int64_t>();
+    vals = values.data_ptr<int64_t>();
+  }
+  const int n = pk::launch_bsi_sort_select(int(mode), reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
+                                           reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+                                           int(slots), int(select_all), int(desc), select_all ? 0 : T, cnt, bo, eb, mp,
+                                           cb, base, cap, cols, vals, cur_stream(views));
+  TORCH_CHECK(n > 0, "bsi_sort_select: not launched");
+  check_launch("bsi_sort_select");
+  return n;
+}
+
 // Extract of a set-like field (rows_extract_kernel, see kernels.h): mode 1 counts into wg[blocks] (zeroed by the
 // caller), mode 2 fills keys[T] behind the bases wg[blocks], mode 3 takes the minimum row id per position into
 // first[>= cap]; D = the rows of views[fview]; columns may be empty (not written).  Returns the workgroups run.
@@ -1340,6 +1392,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bsi_extract", &bsi_extract, "Extract: columns, values and validity of the filter's columns, ascending");
   m.def("extract_slots", [](int64_t depth, int64_t want) { return int64_t(pk::extract_slots(int(depth), int(want))); },
         "Extract: tile slots per workgroup the launcher uses for this depth and request");
+  m.def("bsi_sort_select", &bsi_sort_select, "Sort: count (mode 1) and fill (mode 2) of the selected columns");
+  m.def("sort_slots", [](int64_t depth, int64_t want) { return int64_t(pk::sort_slots(int(depth), int(want))); },
+        "Sort: tile slots per workgroup the launcher uses for this depth and request");
+  m.def("sort_blocks", [](int64_t S, int64_t n) { return pk::sort_blocks(int(S), int(n)); },
+        "Sort: workgroups of one selection launch over S arena shards with n slots each");
   m.def("leaf_src", &leaf_src, "src containers of plain rows straight from the arena (TopN srcs)");
   m.def("row_counts", &row_counts, "row counts of (shard, dense row) entries (device rank caches)");
   m.def("topn_cache_counts", &topn_cache_counts, "cache-only TopN: [candidate x shard] row counts");

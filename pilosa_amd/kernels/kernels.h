@@ -176,6 +176,33 @@ int launch_bsi_extract(const QueryProg* progs, const ViewDev* views, int S, BsiA
                        const int64_t* unit_off, const int64_t* col_base, int64_t base, int64_t cap, uint64_t* columns,
                        int64_t* values, uint8_t* valid, hipStream_t st);
 
+// Sort(<filter>, field=, limit=) (sort_kernels.hip, K29): the selection pass
+// over consider = exists & progs[0] (nprog == 0: exists alone).  The selected
+// columns are those whose base-relative value sorts before T (< T, or > T with
+// desc) and the first m[0] columns, in column order, whose value is T;
+// select_all != 0 selects every considered column and ignores T.  One
+// workgroup per (arena shard, key, slice of n tile slots), sort_blocks(S, n) of
+// them, in column order; both modes must run with the same slots.
+//   mode 1 (count): counts[2 w] / counts[2 w + 1] = workgroup w's columns
+//     before T / equal to T (int32; zeroed by the caller: an empty workgroup
+//     stores nothing).  The other pointers are not read.
+//   mode 2 (fill): before_off / eq_before = the exclusive prefix sums of the
+//     two counts over the workgroups, m = one int64 on the device.  For every
+//     selected column, in ascending column order, columns[o] = its global
+//     column id (col_base[s] + the column's offset in arena shard s) and
+//     values[o] = its real value (base applied).  cap = the length of both
+//     vectors: no store goes past it.
+// depth <= SORT_MAX_PLANES and |T| < 2^32.  slots as for launch_bsi_distinct,
+// clamped by sort_slots().  Returns the slots used, -1 when nothing was
+// launched.
+constexpr int SORT_MAX_PLANES = 32;
+int sort_slots(int depth, int want);
+int64_t sort_blocks(int S, int n);
+int launch_bsi_sort_select(int mode, const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots,
+                           int select_all, int desc, int64_t T, int32_t* counts, const int64_t* before_off,
+                           const int64_t* eq_before, const int64_t* m, const int64_t* col_base, int64_t base,
+                           int64_t cap, int64_t* columns, int64_t* values, hipStream_t st);
+
 // Extract(filter, Rows(field=)) for a set-like field (extract_rows_kernels.hip,
 // K28): every hit of a dense row d < D of views[fview] on the filter progs[0]
 // at an output position pos < cap (unit_off / col_base / the positions as for

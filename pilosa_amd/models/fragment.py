@@ -821,6 +821,25 @@ class Fragment:
         vals[~valid] = 0
         return vals, valid
 
+    def sort_values(self, filt: Optional[Row], bit_depth: int, window: Optional[int] = None,
+                    desc: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+        """The columns of ``exists & filt`` ordered by their base-relative
+        value (descending with ``desc``), ties by column ascending, cut to the
+        first ``window`` (None: all): (uint64 columns, int64 values).  The
+        values come through the per-plane gather of extract_values, so the
+        cost is (considered columns) x bit_depth."""
+        consider = self.row(BSI_EXISTS_BIT)
+        if filt is not None:
+            consider = consider.intersect(filt)
+        cols = consider.columns()
+        if not len(cols) or window == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, np.int64)
+        vals, _ = self.extract_values(cols, bit_depth)
+        order = np.lexsort((cols, ~vals if desc else vals))   # ~v = -v - 1: descending, no overflow
+        if window is not None:
+            order = order[:window]
+        return cols[order], vals[order]
+
     def extract_rows(self, columns: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         """The rows holding each of the ascending ``columns`` of this shard, as
         CSR: (int64 offsets[len + 1], uint64 rows), the rows of a column

@@ -2036,8 +2036,8 @@ class GpuEngine:
             ordered[slot] = views[vid]
         return progs, ordered
 
-    def bsi_kth(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, num: int,
-                den: int) -> Optional[Tuple[int, int]]:
+    def bsi_kth(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, num: int = 0,
+                den: int = 1, rank=None):
         """The k-th smallest base-relative value of exists & filter, k =
         max(1, ceil(N * num / den)) (nearest rank; num / den = nth / 100 as an
         exact fraction): (value, columns holding it), None when no column is
@@ -2046,6 +2046,12 @@ class GpuEngine:
         from them); then one bsi_kth_step launch per bit, MSB first, back to
         back; the bit counts come back in one D2H and the chain is replayed
         on the host (kernels.h kth_chain).
+
+        ``rank`` asks for an absolute rank instead: a function of N that
+        returns the 1-based rank sought in [1, N], or None for "no descent".
+        The answer is then (N, value, columns holding it, the uploaded filter
+        program and views) with value None where no descent ran -- N == 0
+        included -- so that a caller (bsi_sort) can go on from N.
 
         The candidate buffer is S * 128 KiB of device memory (125 MB at 954
         shards) allocated per request from torch's caching allocator, outside
@@ -2056,7 +2062,7 @@ class GpuEngine:
         progs, ordered = self._bsi_filter_program(filt, bsi_view)
         args = self.bsi_args(bsi_view, depth)
         if not S or args[2] < 0:
-            return None
+            return None if rank is None else (0, None, 0, None)
         cand = torch.empty(S * 16 * 1024, dtype=torch.int64, device=self.device)
         cnt = torch.zeros(66, dtype=torch.int64, device=self.device)
         tp, tv = self.upload_batch(progs, ordered)
@@ -2064,10 +2070,16 @@ class GpuEngine:
         self.ext.bsi_kth_init(tp, tv, S, targs, cand, cnt)
         n, nneg = (int(x) for x in self.to_host(cnt[:2]).tolist())
         if n <= 0:
-            return None
+            return None if rank is None else (0, None, 0, (tp, tv, targs))
         from pilosa_amd.executor import nearest_rank
         from .bsi import kth_plan
-        largest, r, tot = kth_plan(nearest_rank(num, den, n), n, nneg)
+        if rank is None:
+            k = nearest_rank(num, den, n)
+        else:
+            k = rank(n)
+            if k is None:
+                return n, None, 0, (tp, tv, targs)
+        largest, r, tot = kth_plan(k, n, nneg)
         largest = int(largest)
         if depth > 0:
             self.ext.bsi_kth_steps(tv, S, targs, cand, cnt, r, tot, largest)
@@ -2075,7 +2087,98 @@ class GpuEngine:
         else:
             cnt1 = torch.zeros(0, dtype=torch.int64)
         mag, count = self.ext.bsi_kth_replay(cnt1.contiguous(), depth, r, tot, largest)
-        return (-int(mag) if largest else int(mag)), int(count)
+        value = -int(mag) if largest else int(mag)
+        if rank is None:
+            return value, int(count)
+        return n, value, int(count), (tp, tv, targs)
+
+    # bit planes bsi_sort_select_kernel compares and transposes at most (kernels.h SORT_MAX_PLANES)
+    SORT_MAX_PLANES = 32
+
+    def bsi_sort(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, base: int,
+                 window: Optional[int], desc: bool, skip: int = 0, slots: int = 0, guard=None):
+        """Sort(): the first ``window`` (None: all) columns of exists & filter
+        over the local shards ordered by value -- descending with ``desc`` --
+        and column, without the first ``skip`` of them: (uint64 columns, int64
+        real values, launches run).
+
+        1. bsi_kth with an absolute rank: bsi_kth_init counts the considered
+           columns, N (``guard(N)``, the size guard, runs here when there is
+           no window); k = min(window, N).  Where k < N the descent returns
+           the threshold T, the value of rank k ascending or N - k + 1
+           descending; where k >= N everything considered is selected and no
+           descent runs.
+        2. bsi_sort_select_kernel, count mode: int32 (before, equal) counts
+           per workgroup; device cumsums turn them into the workgroups'
+           offsets and the tie quota m = k - total(before), which stays on
+           the device.
+        3. bsi_sort_select_kernel, fill mode: the k selected (column, value)
+           pairs in column order into vectors initialised to column -1 and a
+           value that sorts last.
+        4. one stable torch.sort of the k values (of their complement ~v =
+           -v - 1 when descending, which cannot overflow) gives the answer
+           order with ties by column; ``skip`` is cut on the device.
+
+        Device-to-host reads: N and Nneg (16 bytes), the descent's bit counts
+        (8 * depth bytes, only where it runs) and the answer (one copy of both
+        vectors); the totals of the count pass are never read.  An entry whose
+        column is still -1 (data changed between the two launches) is dropped
+        on the host.
+
+        Next to the candidate buffer of the descent (bsi_kth) the request
+        holds 24 bytes per workgroup and 16 bytes per selected entry plus the
+        sort's temporaries, from torch's caching allocator, outside the
+        arenas' ``hbm_budget``."""
+        torch = self.torch
+        from pilosa_amd import shardwidth
+        none = (np.zeros(0, np.uint64), np.zeros(0, np.int64))
+        if depth < 0 or depth > self.SORT_MAX_PLANES:
+            raise NotImplementedError("bit depth beyond the transpose")
+        S = bsi_view.S
+
+        def rank(n):
+            if window is None and guard is not None:
+                guard(n)
+            if window is None or window >= n:
+                return None
+            if window == 0:
+                return None
+            return window if not desc else n - window + 1
+
+        n, T, _, up = self.bsi_kth(filt, bsi_view, depth, rank=rank)
+        launches = 1 if up is not None else 0
+        k = n if window is None else min(int(window), n)
+        if k <= 0 or skip >= k:
+            return none[0], none[1], launches
+        if T is not None:
+            launches += depth
+        tp, tv, targs = up
+        n_slots = int(self.ext.sort_slots(depth, int(slots)))
+        blocks = int(self.ext.sort_blocks(S, n_slots))
+        counts = torch.zeros(blocks * 2, dtype=torch.int32, device=self.device)
+        e64 = torch.empty(0, dtype=torch.int64, device=self.device)
+        select_all = T is None
+        self.ext.bsi_sort_select(1, tp, tv, S, targs, n_slots, select_all, bool(desc), int(T or 0), counts,
+                                 e64, e64, e64, e64, 0, e64, e64)
+        c64 = counts.view(blocks, 2).to(torch.int64)
+        ends = torch.cumsum(c64, 0)
+        offs = ends - c64
+        m = (k - ends[-1, 0]).clamp(min=0).reshape(1).contiguous()
+        col_base = torch.from_numpy(np.asarray(bsi_view.shards, dtype=np.int64) *
+                                    shardwidth.ARENA_WIDTH).to(self.device)
+        columns = torch.full((k,), -1, dtype=torch.int64, device=self.device)
+        info = torch.iinfo(torch.int64)
+        values = torch.full((k,), info.min if desc else info.max, dtype=torch.int64, device=self.device)
+        self.ext.bsi_sort_select(2, tp, tv, S, targs, n_slots, select_all, bool(desc), int(T or 0), counts,
+                                 offs[:, 0].contiguous(), offs[:, 1].contiguous(), m, col_base, int(base), columns,
+                                 values)
+        launches += 2
+        order = torch.sort(~values if desc else values, stable=True).indices[int(skip):]
+        both = self.to_host(torch.stack([columns[order], values[order]])).numpy()
+        live = both[0] != -1
+        if not live.all():
+            both = both[:, live]
+        return both[0].view(np.uint64).copy(), both[1].copy(), launches
 
     # bit planes bsi_distinct_kernel transposes at most (kernels.h DISTINCT_MAX_PLANES)
     DISTINCT_MAX_PLANES = 32

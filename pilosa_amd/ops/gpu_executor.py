@@ -18,6 +18,10 @@ device arenas of the involved field-views:
                 (planes staged, transposed, written compacted in column order)
                 and rows_extract_kernel for set, time, mutex and bool fields
                 (filter tile and rank table staged, every row streamed past)
+* ``bsi_sort``  Sort(<filter>, field=f, limit=n) -> the bsi_kth descent to the
+                threshold value, then two bsi_sort_select_kernel passes (count,
+                fill: planes staged, compared bit-sliced, the selected columns
+                transposed and written in column order) and one device sort
 * ``topk``      TopK(<filter>, field=f, k=n)           -> row_filter_counts (one
                 pass: filter staged per (shard, key), every row streamed past)
 * ``topn``      TopN phase-1/phase-2 with src          -> slot-index LDS
@@ -120,6 +124,23 @@ def extract_slots_env() -> int:
     except ValueError:
         return EXTRACT_SLOTS_DEFAULT
     return v if v in (1, 2, 4, 8) else EXTRACT_SLOTS_DEFAULT
+
+
+# tile slots per workgroup of bsi_sort_select_kernel: 4 measured 9% faster under a
+# filter and 1 to 2% slower without one, 0.04 ms of a 2 ms request, at the one
+# limit swept (profiles/sort/README.md); 1 is what K26 and K27 ship with
+SORT_SLOTS_DEFAULT = 1
+
+
+def sort_slots_env() -> int:
+    """PILOSA_SORT_SLOTS: tile slots per workgroup of bsi_sort_select_kernel
+    (1, 2, 4 or 8, clamped by the launcher to what fits the LDS at the field's
+    depth); anything else means SORT_SLOTS_DEFAULT."""
+    try:
+        v = int(os.environ.get("PILOSA_SORT_SLOTS", "") or SORT_SLOTS_DEFAULT)
+    except ValueError:
+        return SORT_SLOTS_DEFAULT
+    return v if v in (1, 2, 4, 8) else SORT_SLOTS_DEFAULT
 
 
 # Extract(): set, time, mutex and bool fields through rows_extract_kernel (K28)
@@ -255,6 +276,7 @@ class GpuExecutor:
         self.distinct_device = 0         # Distinct() map steps answered by bsi_distinct (K26)
         self.extract_device = 0          # Extract() (map step, int field) pairs answered by bsi_extract (K27)
         self.extract_rows_device = 0     # ... (map step, set-like field) pairs answered by rows_extract (K28)
+        self.sort_device = 0             # Sort() map steps answered by bsi_sort (K29)
         self.topk_device = 0             # TopK() map steps answered by row_filter_counts_kernel
         self.topk_programs = 0           # ... and by the per-row programs route
         # serving Count text path: host prep (parse..launch) vs result wait
@@ -478,7 +500,7 @@ class GpuExecutor:
                 "deviceWriteLaunches": self.device_write_launches, "evictions": self.evictions, "hbmBudget": self.hbm_budget,
                 "percentileDevice": self.percentile_device, "distinctDevice": self.distinct_device,
                 "extractDevice": self.extract_device, "extractRowsDevice": self.extract_rows_device,
-                "extractRowsLaunches": self.engine.rows_extract_launches,
+                "extractRowsLaunches": self.engine.rows_extract_launches, "sortDevice": self.sort_device,
                 "groupSumDevice": self.group_sum_device,
                 "groupSumPerFilter": self.group_sum_per_filter, "topkDevice": self.topk_device,
                 "topkPrograms": self.topk_programs}
@@ -808,6 +830,39 @@ class GpuExecutor:
             for i, vec in zip(rest, extract_fields_host(self.holder, index, [fields[i] for i in rest], cols)):
                 data[i] = vec
         return ExtractedTable(names, cols, data)
+
+    def bsi_sort(self, index: str, c: Call, fname: str, b, window: Optional[int], desc: bool, shards: List[int],
+                 guard=None, skip: int = 0):
+        """Sort(<filter>, field=, ...) over the local shards -> ONE
+        SortedColumns of the first ``window`` entries (None: all) in answer
+        order, without the first ``skip``: the global rank descent to the
+        threshold value, two bsi_sort_select_kernel passes (K29) and one
+        stable device sort (GpuEngine.bsi_sort, which runs ``guard`` on the
+        count of the considered columns when there is no window).  A field
+        without a BSI group or deeper than 32 bits, a filter the planner
+        cannot take and a CompileError leave the map step to the host.
+        PILOSA_SORT_SLOTS sets the tile slots per workgroup."""
+        from pilosa_amd.executor import SortedColumns
+        if b is None or b.bit_depth > GpuEngine.SORT_MAX_PLANES or len(c.children) > 1:
+            raise NotImplementedError
+        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
+        if bv is None:
+            self.sort_device += 1   # no BSI view: answered here, without a launch
+            return SortedColumns()
+        filt = None
+        if len(c.children) == 1:
+            filt = self.plan(index, c.children[0], shards)
+            if filt is EMPTY:
+                self.sort_device += 1   # a filter known empty from the schema: no launch either
+                return SortedColumns()
+        try:
+            cols, vals, launches = self.engine.bsi_sort(filt, bv, b.bit_depth, b.base, window, desc, skip,
+                                                        sort_slots_env(), guard)
+        except CompileError:
+            raise NotImplementedError
+        self.sort_device += 1
+        self.launches += launches
+        return SortedColumns(cols, vals)
 
     def hbm_bytes(self) -> int:
         with self.mu:

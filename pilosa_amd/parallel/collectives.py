@@ -714,6 +714,8 @@ TAG_SIGNED_ROW = 12
 # the JSON [[name, type], ...]] + those bytes + columns[n] + per field (values[n],
 # valid[n]) for a scalar type, (offsets[n + 1], rows[offsets[n]]) for a list type
 TAG_EXTRACT = 13
+# Sort()'s SortedColumns (untranslated): [tag, n] + columns[n] + values[n]
+TAG_SORTED = 14
 
 
 def encode_row_block(blk, device):
@@ -751,7 +753,8 @@ def _words_to_bytes(w: np.ndarray, n: int) -> bytes:
 
 def encode_partial(obj) -> np.ndarray:
     """One rank's partial result -> int64[...] (see the TAG_ layout)."""
-    from pilosa_amd.executor import ExtractedTable, GroupCount, RowIdentifiers, SignedRow, ValCount
+    from pilosa_amd.executor import (ExtractedTable, GroupCount, RowIdentifiers, SignedRow, SortedColumns,
+                                     ValCount)
     from pilosa_amd.models.cache import Pair, PairArray
     from pilosa_amd.models.row import Row
 
@@ -767,6 +770,10 @@ def encode_partial(obj) -> np.ndarray:
                 a = np.ascontiguousarray(a)
                 segs += [a.view(np.int64) if a.dtype == np.uint64 else a.astype(np.int64), b.astype(np.int64)]
         return np.concatenate(segs)
+
+    if isinstance(obj, SortedColumns) and obj.keys is None:
+        return np.concatenate([np.array([TAG_SORTED, len(obj.columns)], np.int64), obj.columns.view(np.int64),
+                               obj.values])
 
     def msg():
         b = encode(obj)
@@ -829,7 +836,8 @@ def encode_partial(obj) -> np.ndarray:
 def decode_partial(w: np.ndarray):
     """Inverse of :func:`encode_partial`."""
     from pilosa_amd import _roaring
-    from pilosa_amd.executor import ExtractedTable, FieldRow, GroupCount, RowIdentifiers, SignedRow, ValCount
+    from pilosa_amd.executor import (ExtractedTable, FieldRow, GroupCount, RowIdentifiers, SignedRow,
+                                     SortedColumns, ValCount)
     from pilosa_amd.models.cache import Pair
     from pilosa_amd.models.row import Row
 
@@ -929,6 +937,9 @@ def decode_partial(w: np.ndarray):
                 o += 2 * n
         assert len(fields) == nf
         return ExtractedTable(fields, cols, data)
+    if tag == TAG_SORTED:
+        n = int(w[1])
+        return SortedColumns(w[2:2 + n].view(np.uint64).copy(), w[2 + n:2 + 2 * n].copy())
     if tag == TAG_SIGNED_ROW:
         pos, o = row_body(1)
         return SignedRow(pos, row_body(o)[0])

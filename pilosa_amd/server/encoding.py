@@ -5,7 +5,7 @@ from __future__ import annotations
 from typing import Any, List, Optional
 
 from pilosa_amd.executor import (ExtractedTable, FieldRow, GroupCount, QueryResponse, RowIdentifiers, SignedRow,
-                                 ValCount)
+                                 SortedColumns, ValCount)
 from pilosa_amd.models.cache import Pair, PairArray
 from pilosa_amd.models.row import Row
 from pilosa_amd.wire import (ATTR_TYPE_BOOL, ATTR_TYPE_FLOAT, ATTR_TYPE_INT, ATTR_TYPE_STRING,
@@ -13,7 +13,7 @@ from pilosa_amd.wire import (ATTR_TYPE_BOOL, ATTR_TYPE_FLOAT, ATTR_TYPE_INT, ATT
                              QUERY_RESULT_TYPE_NIL,
                              QUERY_RESULT_TYPE_PAIR, QUERY_RESULT_TYPE_PAIRS, QUERY_RESULT_TYPE_ROW,
                              QUERY_RESULT_TYPE_ROWIDENTIFIERS, QUERY_RESULT_TYPE_ROWIDS, QUERY_RESULT_TYPE_SIGNEDROW,
-                             QUERY_RESULT_TYPE_UINT64, QUERY_RESULT_TYPE_VALCOUNT, pb)
+                             QUERY_RESULT_TYPE_SORTEDCOLUMNS, QUERY_RESULT_TYPE_UINT64, QUERY_RESULT_TYPE_VALCOUNT, pb)
 
 
 def result_to_json(r: Any):
@@ -24,7 +24,7 @@ def result_to_json(r: Any):
     if isinstance(r, int):
         return r
     if isinstance(r, (Row, ValCount, Pair, RowIdentifiers, GroupCount, FieldRow, PairArray, SignedRow,
-                      ExtractedTable)):
+                      ExtractedTable, SortedColumns)):
         return r.to_json()
     if isinstance(r, list):
         return [result_to_json(x) for x in r]
@@ -165,6 +165,12 @@ def result_to_pb(r: Any, call_name: str = ""):
     elif isinstance(r, ExtractedTable):
         m.Type = QUERY_RESULT_TYPE_EXTRACTEDTABLE
         extracted_to_pb(r, m.ExtractedTable)
+    elif isinstance(r, SortedColumns):
+        m.Type = QUERY_RESULT_TYPE_SORTEDCOLUMNS
+        m.SortedColumns.Columns.extend(r.columns.tolist())
+        if r.keys is not None:
+            m.SortedColumns.Keys.extend(r.keys)
+        m.SortedColumns.Values.extend(r.values.tolist())
     elif isinstance(r, Pair):
         m.Type = QUERY_RESULT_TYPE_PAIR
         m.Pairs.add(ID=r.id, Key=r.key, Count=r.count)
@@ -221,6 +227,11 @@ def result_from_pb(m):
                          Row(np.array(list(m.SignedRow.Neg.Columns), dtype=np.uint64)))
     if t == QUERY_RESULT_TYPE_EXTRACTEDTABLE:
         return extracted_from_pb(m.ExtractedTable)
+    if t == QUERY_RESULT_TYPE_SORTEDCOLUMNS:
+        import numpy as np
+        sc = m.SortedColumns
+        return SortedColumns(np.array(sc.Columns, dtype=np.uint64), np.array(sc.Values, dtype=np.int64),
+                             list(sc.Keys) if len(sc.Keys) else None)
     if t == QUERY_RESULT_TYPE_PAIR:
         p = m.Pairs[0]
         return Pair(p.ID, p.Count, p.Key)

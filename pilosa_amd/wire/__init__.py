@@ -90,6 +90,7 @@ QUERY_RESULT_TYPE_ROWIDENTIFIERS = 8
 QUERY_RESULT_TYPE_PAIR = 9
 QUERY_RESULT_TYPE_SIGNEDROW = 10   # pilosa_amd extension (Distinct)
 QUERY_RESULT_TYPE_EXTRACTEDTABLE = 11   # pilosa_amd extension (Extract)
+QUERY_RESULT_TYPE_SORTEDCOLUMNS = 12   # pilosa_amd extension (Sort)
 
 # Attr.Type codes
 ATTR_TYPE_STRING = 1
