@@ -175,8 +175,10 @@ _EXTRACT_SCALAR = {"int64": np.int64, "uint64": np.uint64, "bool": np.bool_}
 class ExtractedTable:
     """Extract()'s result: the values of some fields for some columns,
     column-major.  ``fields`` is the (name, type) pairs in the order written,
-    ``columns`` the ascending uint64 column ids (``keys`` their string keys on
-    a keyed index, set by the key translation), ``data`` one vector per field:
+    ``columns`` the uint64 column ids -- ascending, except under a Sort child
+    (Extract(Sort(...), ...)), where they are in the Sort's order -- (``keys``
+    their string keys on a keyed index, set by the key translation), ``data``
+    one vector per field:
 
     * a scalar type ("int64", "uint64", "bool"; "string" once a keyed mutex is
       translated): ``(values, valid)``, the value array -- a list of str for
@@ -429,6 +431,71 @@ def sort_guard(n: int):
 
 def _sort_device() -> bool:
     return os.environ.get("PILOSA_SORT_DEVICE", _SORT_DEVICE_DEFAULT) not in ("0", "")
+
+
+def _const_row_max_columns() -> int:
+    """PILOSA_CONSTROW_MAX_COLUMNS: the most columns one ConstRow() lists
+    (default 2^20: a memory choice, not a measured optimum)."""
+    try:
+        v = int(os.environ.get("PILOSA_CONSTROW_MAX_COLUMNS", "") or (1 << 20))
+    except ValueError:
+        return 1 << 20
+    return v if v >= 0 else 1 << 20
+
+
+def const_row_guard(n: int):
+    cap = _const_row_max_columns()
+    if n > cap:
+        raise PilosaError(f"ConstRow(): {n} columns exceed the limit of {cap}")
+
+
+class _ConstRowMemo:
+    """What one ConstRow call object derived from its list: the list it was
+    derived from (the key, by identity: translation replaces a call's list, no
+    code edits one in place), the sorted array once some shard has computed
+    it, and the lock the call's other shards wait on meanwhile."""
+    __slots__ = ("listed", "cols", "lock")
+
+    def __init__(self, listed, cols=None):
+        self.listed = listed
+        self.cols = cols
+        self.lock = threading.Lock()
+
+
+_CONST_ROW_MEMO_LOCK = threading.Lock()   # held only while a call gets its memo object
+
+
+def const_row_columns(c: Call) -> np.ndarray:
+    """ConstRow()'s argument checks -> the listed columns, ascending and
+    distinct, as uint64.  The array is computed once per call object (every
+    shard's map step cuts its slice from it) and kept on ``c.memo``; the
+    shards of one map step arrive together, so the first sorts and the rest
+    wait on that call's own lock, not on other requests."""
+    for k in c.args:
+        if k != "columns":
+            raise PilosaError(f'ConstRow(): unknown argument "{k}"')
+    if c.children:
+        raise PilosaError("ConstRow() accepts no bitmap input")
+    if "columns" not in c.args:
+        raise PilosaError("ConstRow(): columns required")
+    v = c.args["columns"]
+    memo = c.memo
+    if memo is None or memo.listed is not v:
+        with _CONST_ROW_MEMO_LOCK:
+            memo = c.memo
+            if memo is None or memo.listed is not v:
+                memo = c.memo = _ConstRowMemo(v)
+    cols = memo.cols
+    if cols is not None:
+        return cols
+    with memo.lock:
+        if memo.cols is None:
+            # (PQL integers are int64, and the call travels to other nodes as text)
+            if not isinstance(v, list) or not all(type(x) is int and 0 <= x < (1 << 63) for x in v):
+                raise PilosaError("ConstRow(): columns must be a list of unsigned integers")
+            const_row_guard(len(v))
+            memo.cols = np.unique(np.array(v, dtype=np.uint64)) if v else np.zeros(0, np.uint64)
+        return memo.cols
 
 
 class RowIdentifiers:
@@ -1406,6 +1473,13 @@ class Executor:
                 raise PilosaError("cannot shift by negative values")
             r = self.bitmap_call_shard(index, c.children[0], shard)
             return r.shift(k)
+        if n == "ConstRow":
+            # the literal row's segment in this shard: a slice of the sorted list
+            cols = const_row_columns(c)
+            lo = int(np.searchsorted(cols, np.uint64(shard * SHARD_WIDTH)))
+            end = (shard + 1) * SHARD_WIDTH
+            hi = int(np.searchsorted(cols, np.uint64(end))) if end < (1 << 63) else len(cols)
+            return Row.from_segment(shard, _roaring.Bitmap(cols[lo:hi])) if hi > lo else Row()
         raise PilosaError(f"unknown call: {n}")
 
     def time_views(self, f, c: Call) -> Optional[List[str]]:
@@ -1869,6 +1943,9 @@ class Executor:
         The size guard (PILOSA_EXTRACT_MAX_COLUMNS) runs before anything is
         gathered: on the window when ``limit`` is given, else on the filter's
         count."""
+        others = [ch for ch in c.children if ch.name != "Rows"]
+        if len(others) == 1 and others[0].name == "Sort":
+            return self._extract_sorted(index, c, others[0], shards, opt)
         filt, fields, offset, limit = self.extract_params(index, c)
         window = None if limit is None else offset + limit
         use_gpu = self.gpu is not None and _extract_device()
@@ -1919,6 +1996,43 @@ class Executor:
             r = ExtractedTable(names)
         r = r.slice(0, window)
         return r if opt.remote else r.slice(offset)
+
+    def _extract_sorted(self, index: str, c: Call, sort_call: Call, shards, opt) -> ExtractedTable:
+        """Extract(Sort(...), Rows(field=)+, [limit=], [offset=]): the
+        considered columns are the Sort's answer in its order (after its own
+        offset / limit), cut by Extract's offset / limit; the table's columns
+        are in that order.
+
+        Resolved by the coordinating node in two phases, each a call that
+        runs on every route: the Sort, then Extract(ConstRow(columns=<its
+        columns, ascending>), Rows...) over the same shards, then a reorder of
+        the ascending table.  Other nodes only ever see those two calls.
+        Extract's size guard applies to the columns left after the cuts."""
+        if opt.remote:
+            raise PilosaError("Extract(Sort()) is resolved by the coordinating node, not forwarded")
+        self.sort_params(index, sort_call)
+        _, fields, offset, limit = self.extract_params(index, c)
+        names = [(f.name, extract_field_type(f)) for f in fields]
+        sc = self._sort(index, sort_call, shards, opt)
+        ordered = sc.columns[offset:None if limit is None else offset + limit]
+        if not len(ordered):
+            return ExtractedTable(names)
+        extract_guard(len(ordered))
+        ids = np.unique(ordered)
+        # ConstRow's own checks, here as on the nodes and ranks that parse the
+        # call from its text: one node and a cluster give the same answer
+        const_row_guard(len(ids))
+        if int(ids[-1]) >= (1 << 63):
+            raise PilosaError("ConstRow(): columns must be a list of unsigned integers")
+        listed = ids.tolist()
+        const = Call("ConstRow", {"columns": listed})
+        const.memo = _ConstRowMemo(listed, ids)   # sorted already: the local map steps skip the sort
+        inner = Call("Extract", {"limit": len(listed)},
+                     [const] + [ch.clone() for ch in c.children if ch.name == "Rows"])
+        table = self._extract(index, inner, shards, opt)
+        if len(table) != len(ids):
+            raise PilosaError(f"Extract(Sort()): {len(ids)} sorted columns, {len(table)} extracted")
+        return table.take(np.searchsorted(table.columns, ordered))
 
     # ================================================================ Sort
     def sort_params(self, index: str, c: Call):
@@ -2635,6 +2749,16 @@ class Executor:
             row_key, col_key = "previous", "column"
         elif n == "GroupBy":
             return self._translate_group_by(index, idx, c)
+        elif n == "ConstRow":
+            v = c.args.get("columns")
+            if isinstance(v, list):
+                if idx.keys:
+                    if not all(isinstance(x, str) for x in v):
+                        raise BadRequestError("column value must be a string when index 'keys' option enabled")
+                    c.args["columns"] = [int(x) for x in ts.translate_columns_to_uint64(index, v)] if v else []
+                elif any(isinstance(x, str) for x in v):
+                    raise BadRequestError("string 'col' value not allowed unless index 'keys' option enabled")
+            return
         else:
             col_key = "col"
             fname = c.args.get("field") if isinstance(c.args.get("field"), str) else ""

@@ -1215,6 +1215,24 @@ void shift_dense(torch::Tensor src, int64_t S, int64_t n, torch::Tensor main_out
   check_launch("shift_dense");
 }
 
+// ConstRow(columns=[...]): the dense one-row view of the columns at the
+// ascending locations loc[0, n) (const_row_kernel, K30)
+void const_row(torch::Tensor loc, int64_t n, int64_t S, torch::Tensor payload, torch::Tensor meta) {
+  check_dev(loc, "const_row loc");
+  check_dev(payload, "const_row payload");
+  check_dev(meta, "const_row meta");
+  TORCH_CHECK(S >= 1 && S < (int64_t(1) << 27), "const_row: S out of range");
+  TORCH_CHECK(loc.scalar_type() == torch::kInt64 && loc.is_contiguous() && n >= 0 && loc.numel() >= n,
+              "const_row loc int64[n]");
+  TORCH_CHECK(payload.scalar_type() == torch::kInt16 && payload.is_contiguous() && payload.numel() == S * 16 * 4096,
+              "const_row payload int16[S*16*4096]");
+  TORCH_CHECK(meta.scalar_type() == torch::kInt64 && meta.is_contiguous() && meta.numel() == S * 16,
+              "const_row meta int64[S*16]");
+  pk::launch_const_row(loc.data_ptr<int64_t>(), n, int(S), reinterpret_cast<uint16_t*>(payload.data_ptr<int16_t>()),
+                       meta.data_ptr<int64_t>(), cur_stream(payload));
+  check_launch("const_row");
+}
+
 void rows_list(torch::Tensor view, int64_t s0, int64_t ns, int64_t j, int64_t col16, torch::Tensor flags) {
   check_dev(flags, "flags");
   const pk::ViewDev v = viewdev_from(view);
@@ -1426,6 +1444,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("shift_dense", &shift_dense, "Shift a dense view by n columns per shard (main + next-shard spill)",
         py::arg("src"), py::arg("S"), py::arg("n"), py::arg("main_out"), py::arg("main_meta"), py::arg("spill_out"),
         py::arg("spill_meta"), py::arg("M") = 1, py::arg("row_words") = 16384);
+  m.def("const_row", &const_row, "ConstRow: a column list as a dense one-row view (one bitmap per shard and key)");
   m.def("rows_list", &rows_list, "flag dense rows with non-empty containers (optionally holding one column)");
   m.def("rows_extract", &rows_extract,
         "Extract: the rows of a set-like field per filter column (count / fill / scalar)");

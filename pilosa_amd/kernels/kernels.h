@@ -344,6 +344,10 @@ void launch_expr_dense(const QueryProg* progs, int Q, const ViewDev* views, int 
 // next shard (both dense, with metadata like launch_expr_dense).
 void launch_shift_dense(const uint64_t* src, int S, int M, int64_t n, int64_t row_words, uint64_t* main_out,
                         int64_t* main_meta, uint64_t* spill_out, int64_t* spill_meta, hipStream_t st);
+// ConstRow (const_row_kernels.hip, K30): the columns at the ascending
+// locations loc[0, n) (si << 20 | offset) as a dense one-row view, one bitmap
+// and one meta word per (shard, key) unit, every unit written.
+void launch_const_row(const int64_t* loc, int64_t n, int S, uint16_t* payload, int64_t* meta, hipStream_t st);
 // Rows listing: flags[d] = 1 for dense rows with a non-empty container in
 // shards [s0, s0 + ns) (j >= 0: only rows whose key-j container holds col16).
 void launch_rows(const ViewDev& v, int s0, int ns, int j, uint32_t col16, uint8_t* flags, hipStream_t st);

@@ -1865,6 +1865,45 @@ class GpuEngine:
         sb = torch.arange(S + 1, dtype=torch.int64, device=self.device) * 16
         return DeviceView.from_device(np.zeros(1, np.uint64), rowptr, sb, meta, payload, self.device, shards, S * 16)
 
+    def const_row_view(self, cols: np.ndarray, shards: Sequence[int]) -> Optional["DeviceView"]:
+        """ConstRow: the listed global columns ``cols`` (uint64) over the
+        device shards ``shards`` as a dense one-row view (const_row_kernel,
+        K30), None when no listed column falls into them (nothing is launched).
+
+        A column's device shard is col // ARENA_WIDTH and its offset col %
+        ARENA_WIDTH (a narrow shard fills the first containers of its device
+        shard, a wide one is several device shards); columns of device shards
+        outside ``shards`` are dropped.  The kernel reads the locations ``si <<
+        20 | offset`` ascending, one int64 each, and writes every unit of the
+        view, so the buffers are not cleared first.  The view is S x (128 KiB +
+        128 B) from the caching allocator, outside the arena budget, and is
+        not cached: its key would be the whole list."""
+        from pilosa_amd import shardwidth
+        torch = self.torch
+        S = len(shards)
+        cols = np.asarray(cols, dtype=np.uint64)
+        if not S or not len(cols):
+            return None
+        sh = np.asarray([int(s) for s in shards], dtype=np.uint64)
+        order = np.argsort(sh, kind="stable")
+        sh = sh[order]
+        width = np.uint64(shardwidth.ARENA_WIDTH.bit_length() - 1)   # the arena width is a power of two
+        ds = cols >> width
+        pos = np.minimum(np.searchsorted(sh, ds), S - 1)
+        keep = sh[pos] == ds
+        if not keep.any():
+            return None
+        si = order[pos[keep]].astype(np.int64)
+        x = (cols[keep] & np.uint64(shardwidth.ARENA_WIDTH - 1)).astype(np.int64)
+        loc = (si << 20) | x
+        # ascending columns over an ascending shard list (what the planner passes) are ascending already
+        if len(loc) > 1 and not bool((loc[1:] > loc[:-1]).all()):
+            loc = np.sort(loc)
+        payload = torch.empty(S * 16 * 4096, dtype=torch.int16, device=self.device)
+        meta = torch.empty(S * 16, dtype=torch.int64, device=self.device)
+        self.ext.const_row(self._h2d(loc.view(np.uint8)).view(torch.int64), len(loc), S, payload, meta)
+        return self._one_row_view(payload, meta, [int(s) for s in shards])
+
     def dense_view(self, expr) -> "DeviceView":
         """Evaluate one expression over every local shard into a dense one-row
         view (expr_dense_kernel)."""

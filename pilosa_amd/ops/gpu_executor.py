@@ -156,6 +156,23 @@ def extract_rows_device() -> bool:
     return os.environ.get("PILOSA_EXTRACT_ROWS_DEVICE", EXTRACT_ROWS_DEVICE_DEFAULT) not in ("0", "")
 
 
+# ConstRow(): the literal row written on the device (const_row_kernel, K30) when
+# PILOSA_CONSTROW_DEVICE is unset.  On by default because without it every call
+# holding a ConstRow leaves the device; no measured ratio decides it
+# (profiles/const_row/README.md)
+CONSTROW_DEVICE_DEFAULT = "1"
+
+
+def const_row_device() -> bool:
+    """PILOSA_CONSTROW_DEVICE: 0 sends every call that holds a ConstRow() to
+    the host; unset means CONSTROW_DEVICE_DEFAULT."""
+    return os.environ.get("PILOSA_CONSTROW_DEVICE", CONSTROW_DEVICE_DEFAULT) not in ("0", "")
+
+
+def _holds_const_row(c: Call) -> bool:
+    return c.name == "ConstRow" or any(_holds_const_row(ch) for ch in c.children)
+
+
 class _Empty:
     """Placeholder for a leaf whose field/view does not exist (empty row)."""
 
@@ -277,6 +294,7 @@ class GpuExecutor:
         self.extract_device = 0          # Extract() (map step, int field) pairs answered by bsi_extract (K27)
         self.extract_rows_device = 0     # ... (map step, set-like field) pairs answered by rows_extract (K28)
         self.sort_device = 0             # Sort() map steps answered by bsi_sort (K29)
+        self.const_row_device = 0        # ConstRow() views written by const_row_kernel (K30)
         self.topk_device = 0             # TopK() map steps answered by row_filter_counts_kernel
         self.topk_programs = 0           # ... and by the per-row programs route
         # serving Count text path: host prep (parse..launch) vs result wait
@@ -501,6 +519,7 @@ class GpuExecutor:
                 "percentileDevice": self.percentile_device, "distinctDevice": self.distinct_device,
                 "extractDevice": self.extract_device, "extractRowsDevice": self.extract_rows_device,
                 "extractRowsLaunches": self.engine.rows_extract_launches, "sortDevice": self.sort_device,
+                "constRowDevice": self.const_row_device,
                 "groupSumDevice": self.group_sum_device,
                 "groupSumPerFilter": self.group_sum_per_filter, "topkDevice": self.topk_device,
                 "topkPrograms": self.topk_programs}
@@ -969,6 +988,23 @@ class GpuExecutor:
             if child is EMPTY:
                 return Leaf(ex, 0)
             return Op("andnot", (Leaf(ex, 0), child))
+        if n == "ConstRow":
+            if not const_row_device():
+                raise NotImplementedError
+            from pilosa_amd.executor import const_row_columns
+            try:
+                cols = const_row_columns(c)
+            except PilosaError:
+                raise NotImplementedError   # the host path raises the proper error
+            try:
+                rv = self.engine.const_row_view(cols, shardwidth.device_shards(shards))
+            except CompileError:
+                raise NotImplementedError
+            if rv is None:
+                return EMPTY   # nothing listed in these shards: no launch
+            self.const_row_device += 1
+            self.launches += 1
+            return Leaf(rv, 0)
         raise NotImplementedError(n)
 
     # ------------------------------------------------------------ calls
@@ -1008,6 +1044,8 @@ class GpuExecutor:
         instead of Python planning; any call outside its subset is compiled by
         the planner against the same views, anything else returns None."""
         from .planner import NativeCountCompiler, Unsupported
+        if any(_holds_const_row(c) for c in calls):
+            return None  # outside the native subset; do not print a long list only to have it declined
         views: Dict[str, DeviceView] = {}
         for f in self._native_fields(index):
             dv = self.view_arena(index, f, VIEW_STANDARD, shards)

@@ -62,7 +62,8 @@ MAX_IN_FLIGHT = 4     # count batches a worker keeps in flight before it waits f
 MAX_SHARD_SETS = 4096  # shard lists registered with the ranks (OP_SHARDSET); more go the general way
 CALL_MIN_CAP = 1024    # int64 words per rank of a general call's partial gather (grows per call name)
 # bitmap calls whose rank partial can travel as device container blocks
-_ROW_CALLS = ("Row", "Range", "Bitmap", "Intersect", "Union", "Difference", "Xor", "Not", "Shift")
+_ROW_CALLS = ("Row", "Range", "Bitmap", "Intersect", "Union", "Difference", "Xor", "Not", "Shift",
+              "ConstRow")
 _OP_NAMES = {OP_STOP: "stop", OP_COUNT: "count", OP_CALL: "call", OP_WRITE: "write", OP_IMPORT: "import",
              OP_SCHEMA: "schema", OP_DEL_INDEX: "deleteIndex", OP_DEL_FIELD: "deleteField", OP_SHARDS: "shards",
              OP_COUNT_TEXT: "countText", OP_ERRORS: "errors", OP_TOPN: "topn", OP_SYNC: "sync",

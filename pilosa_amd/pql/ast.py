@@ -55,12 +55,15 @@ def is_reserved_arg(name: str) -> bool:
 
 
 class Call:
-    __slots__ = ("name", "args", "children")
+    # ``memo``: what an executor derived from the arguments once per call
+    # object (ConstRow's sorted column array); not part of the call's value
+    __slots__ = ("name", "args", "children", "memo")
 
     def __init__(self, name: str, args: Optional[Dict[str, Any]] = None, children: Optional[List["Call"]] = None):
         self.name = name
         self.args: Dict[str, Any] = args if args is not None else {}
         self.children: List[Call] = children if children is not None else []
+        self.memo = None
 
     def __eq__(self, other):
         return (isinstance(other, Call) and self.name == other.name and self.args == other.args
