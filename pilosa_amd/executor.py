@@ -1800,9 +1800,7 @@ class Executor:
                 raise
             except Exception as err:  # noqa: BLE001 - counted; the generic path answers
                 self._gpu_fault(err)
-        consider = Call("Row", {fname: Condition(NEQ, None)})
-        if c.children:
-            consider = Call("Intersect", {}, [c.children[0].clone(), consider])
+        consider = self._consider_call(fname, c)
 
         def count(child: Call) -> int:
             return self._count(index, Call("Count", {}, [child]), shards, opt)
@@ -1826,6 +1824,15 @@ class Executor:
                 lo = mid + 1
         cnt = count(Call("Intersect", {}, [consider.clone(), Call("Row", {fname: Condition(EQ, lo)})]))
         return ValCount(lo, cnt) if cnt else ValCount()
+
+    @staticmethod
+    def _consider_call(fname: str, c: Call) -> Call:
+        """The considered set of Percentile() and Sort(): the columns with a
+        value in the field, intersected with the filter child."""
+        consider = Call("Row", {fname: Condition(NEQ, None)})
+        if c.children:
+            consider = Call("Intersect", {}, [c.children[0].clone(), consider])
+        return consider
 
     def _percentile_on_device(self, index, shards, opt) -> bool:
         if self.gpu is None or not _percentile_device() or self._has_remote(index, shards, opt):
@@ -1885,18 +1892,73 @@ class Executor:
         return r or SignedRow()
 
     # ================================================================ Extract
+    @staticmethod
+    def _window_args(name: str, c: Call):
+        """The limit= / offset= checks of Extract() and Sort() -> (offset, limit or None)."""
+        for k in ("limit", "offset"):
+            v = c.args.get(k)
+            if k in c.args and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
+                raise PilosaError(f"{name}(): {k} must be a non-negative integer")
+        return c.args.get("offset") or 0, c.args.get("limit")
+
+    def _windowed_map_reduce(self, index: str, c: Call, shards, opt, offset: int, window, use_gpu: bool, guard,
+                             count_guard, empty, map_fn, combine, device_fn, is_cut=lambda: False):
+        """The shared tail of Extract() and Sort(): the size guard, the map /
+        reduce and the cut to the window.
+
+        ``guard(n)`` runs before anything is gathered: on ``window`` (offset +
+        limit) when there is one, else on the call's count.  Where every shard
+        is local to one device its own count pass delivers that count (the
+        engine runs ``guard`` before its gather), so no extra Count is spent:
+        ``count_guard()``, the Count over all shards, runs only otherwise --
+        and when the device declines or fails before its guard, since the
+        host gather then follows.  ``device_fn(ss)`` is the local map step
+        over all local shards, ``combine(p, v)`` joins two non-empty partials
+        and keeps the window, ``empty`` is the answer without any.  Only the
+        coordinating node applies ``offset``: a node answering a remote or
+        mesh request returns its first ``window`` entries; ``is_cut()`` says
+        that the one local map step has cut both already."""
+        device_guards = False
+        if window is not None:
+            guard(window)
+        elif not opt.remote:
+            device_guards = use_gpu and bool(shards) and not self._use_mesh(opt) and \
+                not self._has_remote(index, shards, opt)
+            if not device_guards:
+                count_guard()
+
+        def reduce_fn(p, v):
+            if v is None or not len(v):
+                return v if p is None else p
+            if p is None or not len(p):
+                return v
+            return combine(p, v)
+
+        def local_fn(ss):
+            try:
+                return device_fn(ss)
+            except PilosaError:
+                raise
+            except Exception:
+                if device_guards:   # the device declined or failed before its guard: the host gather follows
+                    count_guard()
+                raise
+
+        r = self.map_reduce(index, shards, c, opt, map_fn, reduce_fn, local_fn if use_gpu else None)
+        if r is None:
+            r = empty
+        if is_cut():
+            return r
+        r = r.slice(0, window)
+        return r if opt.remote else r.slice(offset)
+
     def extract_params(self, index: str, c: Call):
         """Extract()'s argument checks -> (filter call, [Field], offset, limit
         or None)."""
         for k in c.args:
             if k not in ("limit", "offset"):
                 raise PilosaError(f'Extract(): unknown argument "{k}"')
-        nums = {}
-        for k in ("limit", "offset"):
-            v = c.args.get(k)
-            if k in c.args and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
-                raise PilosaError(f"Extract(): {k} must be a non-negative integer")
-            nums[k] = v
+        offset, limit = self._window_args("Extract", c)
         rows = [ch for ch in c.children if ch.name == "Rows"]
         filters = [ch for ch in c.children if ch.name != "Rows"]
         if not filters:
@@ -1919,7 +1981,7 @@ class Executor:
             if f is None:
                 raise ErrFieldNotFound
             fields.append(f)
-        return filters[0], fields, nums["offset"] or 0, nums["limit"]
+        return filters[0], fields, offset, limit
 
     def _extract(self, index: str, c: Call, shards, opt) -> ExtractedTable:
         """Extract(<one bitmap call>, Rows(field=<name>)+, [limit=], [offset=]):
@@ -1948,24 +2010,10 @@ class Executor:
             return self._extract_sorted(index, c, others[0], shards, opt)
         filt, fields, offset, limit = self.extract_params(index, c)
         window = None if limit is None else offset + limit
-        use_gpu = self.gpu is not None and _extract_device()
+        names = [(f.name, extract_field_type(f)) for f in fields]
 
         def count_guard():
             extract_guard(int(self._count(index, Call("Count", {}, [filt]), shards, opt)))
-
-        # without a limit the guard needs the filter's count.  Where every shard
-        # is local to one device its count pass delivers it (GpuEngine.bsi_extract
-        # runs the guard before the extract pass), so no extra Count is spent --
-        # unless the device declines, see local_fn
-        device_guards = False
-        if window is not None:
-            extract_guard(window)
-        elif not opt.remote:
-            device_guards = use_gpu and bool(shards) and not self._use_mesh(opt) and \
-                not self._has_remote(index, shards, opt)
-            if not device_guards:
-                count_guard()
-        names = [(f.name, extract_field_type(f)) for f in fields]
 
         def map_fn(shard):
             cols = self.bitmap_call_shard(index, filt, shard).columns()
@@ -1974,28 +2022,10 @@ class Executor:
             return ExtractedTable(names, cols, [extract_field_shard(self.holder, index, f, shard, cols)
                                                 for f in fields])
 
-        def reduce_fn(p, v):
-            if v is None or not len(v):
-                return v if p is None else p
-            if p is None or not len(p):
-                return v
-            return ExtractedTable.concat([p, v]).slice(0, window)
-
-        def local_fn(ss):
-            try:
-                return self.gpu.bsi_extract(index, filt, fields, window, ss)
-            except PilosaError:
-                raise
-            except Exception:
-                if device_guards:   # the device declined or failed before its guard: the host gather follows
-                    count_guard()
-                raise
-
-        r = self.map_reduce(index, shards, c, opt, map_fn, reduce_fn, local_fn if use_gpu else None)
-        if r is None:
-            r = ExtractedTable(names)
-        r = r.slice(0, window)
-        return r if opt.remote else r.slice(offset)
+        return self._windowed_map_reduce(
+            index, c, shards, opt, offset, window, self.gpu is not None and _extract_device(), extract_guard,
+            count_guard, ExtractedTable(names), map_fn, lambda p, v: ExtractedTable.concat([p, v]).slice(0, window),
+            lambda ss: self.gpu.bsi_extract(index, filt, fields, window, ss))
 
     def _extract_sorted(self, index: str, c: Call, sort_call: Call, shards, opt) -> ExtractedTable:
         """Extract(Sort(...), Rows(field=)+, [limit=], [offset=]): the
@@ -2044,12 +2074,7 @@ class Executor:
         fname = c.args.get("field")
         if not fname or not isinstance(fname, str):
             raise PilosaError("Sort(): field required")
-        nums = {}
-        for k in ("limit", "offset"):
-            v = c.args.get(k)
-            if k in c.args and (isinstance(v, bool) or not isinstance(v, int) or v < 0):
-                raise PilosaError(f"Sort(): {k} must be a non-negative integer")
-            nums[k] = v
+        offset, limit = self._window_args("Sort", c)
         desc = c.args.get("sort-desc", False)
         if not isinstance(desc, bool):
             raise PilosaError("Sort(): sort-desc must be a boolean")
@@ -2061,7 +2086,7 @@ class Executor:
         b = f.bsi_group(fname)
         if f.type != FIELD_TYPE_INT or b is None:
             raise PilosaError(f'cannot compute Sort() on non-integer field: "{fname}"')
-        return fname, b, nums["offset"] or 0, nums["limit"], desc
+        return fname, b, offset, limit, desc
 
     def _sort(self, index: str, c: Call, shards, opt) -> SortedColumns:
         """Sort(field=<int field>, [limit=], [offset=], [sort-desc=]) and
@@ -2090,24 +2115,9 @@ class Executor:
         the considered columns."""
         fname, b, offset, limit, desc = self.sort_params(index, c)
         window = None if limit is None else offset + limit
-        use_gpu = self.gpu is not None and _sort_device()
 
-        def count_guard():
-            consider = Call("Row", {fname: Condition(NEQ, None)})
-            if c.children:
-                consider = Call("Intersect", {}, [c.children[0].clone(), consider])
-            sort_guard(int(self._count(index, Call("Count", {}, [consider]), shards, opt)))
-
-        # as for Extract(): where every shard is local to one device, its own
-        # count of the considered set (N of bsi_kth_init) feeds the guard
-        device_guards = False
-        if window is not None:
-            sort_guard(window)
-        elif not opt.remote:
-            device_guards = use_gpu and bool(shards) and not self._use_mesh(opt) and \
-                not self._has_remote(index, shards, opt)
-            if not device_guards:
-                count_guard()
+        def count_guard():   # (on the device N of bsi_kth_init feeds the guard)
+            sort_guard(int(self._count(index, Call("Count", {}, [self._consider_call(fname, c)]), shards, opt)))
 
         def map_fn(shard):
             frag = self.holder.fragment(index, fname, VIEW_BSI_PREFIX + fname, shard)
@@ -2116,38 +2126,21 @@ class Executor:
             cols, vals = frag.sort_values(self._bsi_filter_shard(index, c, shard), b.bit_depth, window, desc)
             return SortedColumns(cols, vals + b.base)
 
-        def reduce_fn(p, v):
-            if v is None or not len(v):
-                return v if p is None else p
-            if p is None or not len(p):
-                return v
-            return p.merge(v, window, desc)
-
         # the coordinating node of a request whose shards are all local to one
         # device lets the device cut ``offset`` before its one copy to the host
         alone = not opt.remote and not self.paranoia and not self._use_mesh(opt) and \
             not self._has_remote(index, shards, opt)
         cut = []
 
-        def local_fn(ss):
-            try:
-                r = self.gpu.bsi_sort(index, c, fname, b, window, desc, ss, sort_guard, offset if alone else 0)
-                cut.append(alone)
-                return r
-            except PilosaError:
-                raise
-            except Exception:
-                if device_guards:   # the device declined or failed before its guard: the host gather follows
-                    count_guard()
-                raise
-
-        r = self.map_reduce(index, shards, c, opt, map_fn, reduce_fn, local_fn if use_gpu else None)
-        if r is None:
-            r = SortedColumns()
-        if cut == [True]:   # one local map step, already without the first ``offset`` entries
+        def device_fn(ss):
+            r = self.gpu.bsi_sort(index, c, fname, b, window, desc, ss, sort_guard, offset if alone else 0)
+            cut.append(alone)
             return r
-        r = r.slice(0, window)
-        return r if opt.remote else r.slice(offset)
+
+        # cut == [True]: one local map step, already without the first ``offset`` entries
+        return self._windowed_map_reduce(
+            index, c, shards, opt, offset, window, self.gpu is not None and _sort_device(), sort_guard, count_guard,
+            SortedColumns(), map_fn, lambda p, v: p.merge(v, window, desc), device_fn, lambda: cut == [True])
 
     def _minmax_row(self, index: str, c: Call, shards, opt, is_min: bool) -> Pair:
         fname = c.args.get("field")

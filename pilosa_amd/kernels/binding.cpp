@@ -33,6 +33,37 @@ void check_launch(const char* what) {
   TORCH_CHECK(e == hipSuccess, what, ": kernel launch failed: ", hipGetErrorString(e));
 }
 
+// the packed QueryProg / ViewDev records of a uint8 device tensor
+const pk::QueryProg* progs_of(const torch::Tensor& t) {
+  return reinterpret_cast<const pk::QueryProg*>(t.data_ptr<uint8_t>());
+}
+const pk::ViewDev* views_of(const torch::Tensor& t) { return reinterpret_cast<const pk::ViewDev*>(t.data_ptr<uint8_t>()); }
+
+// The conditions the BSI entry points share.  progs holds the filter program
+// (progs[0]; nprog == 0: no filter).
+void check_filter_prog(const torch::Tensor& progs) {
+  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+}
+void check_shards(int64_t S, int bits, const char* what) {
+  TORCH_CHECK(S >= 0 && S < (int64_t(1) << bits), what, ": shard count");
+}
+void check_view_slot(int64_t slot, const torch::Tensor& views, const char* what) {
+  TORCH_CHECK(slot >= 0 && slot < views.numel() / int64_t(sizeof(pk::ViewDev)), what, ": view slot");
+}
+// a device int64 vector of at least n elements
+void check_i64(const torch::Tensor& t, int64_t n, const char* name) {
+  check_dev(t, name);
+  TORCH_CHECK(t.scalar_type() == torch::kInt64 && t.numel() >= n, name, " must be int64[>= ", n, "]");
+}
+// the optional column vector of the Extract calls: nullptr when empty (not written), else exactly n elements
+// (exact) or at least n
+uint64_t* columns_or_null(const torch::Tensor& columns, int64_t n, bool exact) {
+  if (!columns.numel()) return nullptr;
+  check_i64(columns, n, "columns");
+  TORCH_CHECK(!exact || columns.numel() == n, "columns must be int64[cap] or empty");
+  return reinterpret_cast<uint64_t*>(columns.data_ptr<int64_t>());
+}
+
 // Small host int32 arrays (a batch's parameters) -> a new device tensor on
 // the current stream, staged through a ring of pinned slots: one memcpy and
 // one async H2D, no allocator or Python on the way.  A slot is rewritten only
@@ -178,8 +209,8 @@ void expr_count(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
                 "per_shard must be int64[Q*S]");
     ps = per_shard->data_ptr<int64_t>();
   }
-  pk::launch_expr_count(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), Q,
-                        reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), o, pk_, ps, int(mode),
+  pk::launch_expr_count(progs_of(progs), Q,
+                        views_of(views), int(S), o, pk_, ps, int(mode),
                         cur_stream(progs));
   check_launch("expr_count");
 }
@@ -193,8 +224,8 @@ void expr_materialize(torch::Tensor progs, torch::Tensor views, int64_t S, torch
   check_dev(outp, "outp");
   const int Q = int(progs.numel() / sizeof(pk::QueryProg));
   TORCH_CHECK(counts.numel() >= int64_t(Q) * S * 16 && offs.numel() >= int64_t(Q) * S * 16, "counts/offs size");
-  pk::launch_expr_materialize(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), Q,
-                              reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S),
+  pk::launch_expr_materialize(progs_of(progs), Q,
+                              views_of(views), int(S),
                               counts.data_ptr<int32_t>(), offs.data_ptr<int64_t>(),
                               reinterpret_cast<uint16_t*>(outp.data_ptr<int16_t>()), cur_stream(progs));
   check_launch("expr_materialize");
@@ -222,7 +253,7 @@ void bsi_range(torch::Tensor views, int64_t S, torch::Tensor bsi_args, int64_t o
   TORCH_CHECK(op >= 0 && op <= 7, "bsi op");
   TORCH_CHECK(out_payload.numel() >= S * 16 * 4096 && out_meta.numel() >= S * 16, "bsi_range outputs too small");
   TORCH_CHECK(out_meta.scalar_type() == torch::kInt64, "out_meta must be int64");
-  pk::launch_bsi_range(reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), bsi_args_from(bsi_args),
+  pk::launch_bsi_range(views_of(views), int(S), bsi_args_from(bsi_args),
                        int(op), p1, p2, reinterpret_cast<uint16_t*>(out_payload.data_ptr<int16_t>()),
                        out_meta.data_ptr<int64_t>(), nullptr, cur_stream(views));
   check_launch("bsi_range");
@@ -234,7 +265,7 @@ void bsi_range_count(torch::Tensor views, int64_t S, torch::Tensor bsi_args, int
   check_dev(out_count, "out_count");
   TORCH_CHECK(op >= 0 && op <= 7, "bsi op");
   TORCH_CHECK(out_count.scalar_type() == torch::kInt64 && out_count.numel() >= 1, "out_count int64[1]");
-  pk::launch_bsi_range(reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), bsi_args_from(bsi_args),
+  pk::launch_bsi_range(views_of(views), int(S), bsi_args_from(bsi_args),
                        int(op), p1, p2, nullptr, nullptr,
                        reinterpret_cast<unsigned long long*>(out_count.data_ptr<int64_t>()), cur_stream(views));
   check_launch("bsi_range_count");
@@ -244,24 +275,19 @@ void bsi_minmax(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
                 int64_t which) {
   check_dev(progs, "progs");
   check_dev(views, "views");
-  check_dev(out, "out");
-  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
-  TORCH_CHECK(out.scalar_type() == torch::kInt64 && out.numel() >= S * 16 * 10, "out must be int64[S*16*10]");
-  pk::launch_bsi_minmax(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
-                        reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S),
+  check_filter_prog(progs);
+  check_i64(out, S * 16 * 10, "out");
+  pk::launch_bsi_minmax(progs_of(progs),
+                        views_of(views), int(S),
                         bsi_args_from(bsi_args), out.data_ptr<int64_t>(), cur_stream(views), int(which));
   check_launch("bsi_minmax");
 }
 
 static void check_kth(const torch::Tensor& views, const torch::Tensor& cand, const torch::Tensor& cnt, int64_t S) {
   check_dev(views, "views");
-  check_dev(cand, "cand");
-  check_dev(cnt, "cnt");
-  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 27), "bsi_kth: shard count");
-  TORCH_CHECK(cand.scalar_type() == torch::kInt64 && cand.is_contiguous() && cand.numel() >= S * 16 * 1024,
-              "cand must be int64[S*16*1024]");
-  TORCH_CHECK(cnt.scalar_type() == torch::kInt64 && cnt.is_contiguous() && cnt.numel() >= pk::KTH_CNT,
-              "cnt must be int64[66]");
+  check_shards(S, 27, "bsi_kth");
+  check_i64(cand, S * 16 * 1024, "cand");
+  check_i64(cnt, pk::KTH_CNT, "cnt");
 }
 
 // Percentile: candidates = exists & filter per (shard, key); cnt[0..1] += N, Nneg (cnt zeroed by the caller)
@@ -269,9 +295,9 @@ void bsi_kth_init(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Te
                   torch::Tensor cnt) {
   check_dev(progs, "progs");
   check_kth(views, cand, cnt, S);
-  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
-  pk::launch_bsi_kth_init(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
-                          reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S),
+  check_filter_prog(progs);
+  pk::launch_bsi_kth_init(progs_of(progs),
+                          views_of(views), int(S),
                           bsi_args_from(bsi_args), reinterpret_cast<uint64_t*>(cand.data_ptr<int64_t>()),
                           reinterpret_cast<unsigned long long*>(cnt.data_ptr<int64_t>()), cur_stream(views));
   check_launch("bsi_kth_init");
@@ -285,7 +311,7 @@ void bsi_kth_steps(torch::Tensor views, int64_t S, torch::Tensor bsi_args, torch
   const pk::BsiArgs b = bsi_args_from(bsi_args);
   hipStream_t st = cur_stream(views);
   for (int i = b.depth - 1; i >= 0; i--)
-    pk::launch_bsi_kth_step(reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+    pk::launch_bsi_kth_step(views_of(views), int(S), b,
                             reinterpret_cast<uint64_t*>(cand.data_ptr<int64_t>()),
                             reinterpret_cast<unsigned long long*>(cnt.data_ptr<int64_t>()), i, uint64_t(r),
                             uint64_t(tot), int(largest_first != 0), st);
@@ -314,18 +340,15 @@ int64_t bsi_distinct(torch::Tensor progs, torch::Tensor views, int64_t S, torch:
                      int64_t mark, torch::Tensor pos, torch::Tensor neg) {
   check_dev(progs, "progs");
   check_dev(views, "views");
-  check_dev(pos, "pos");
-  check_dev(neg, "neg");
-  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24), "bsi_distinct: shard count");
-  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  check_shards(S, 24, "bsi_distinct");
+  check_filter_prog(progs);
   const pk::BsiArgs b = bsi_args_from(bsi_args);
   TORCH_CHECK(b.depth >= 0 && b.depth <= pk::DISTINCT_MAX_PLANES, "bsi_distinct: bit depth");
-  const int64_t words = std::max<int64_t>(1, (int64_t(1) << b.depth) >> 6);
-  for (const torch::Tensor* t : {&pos, &neg})
-    TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->is_contiguous() && t->numel() >= words,
-                "pos / neg must be int64[max(1, 2^depth / 64)]");
-  const int n = pk::launch_bsi_distinct(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
-                                        reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+  const int64_t words = std::max<int64_t>(1, (int64_t(1) << b.depth) >> 6);  // 2^depth bits each
+  check_i64(pos, words, "pos");
+  check_i64(neg, words, "neg");
+  const int n = pk::launch_bsi_distinct(progs_of(progs),
+                                        views_of(views), int(S), b,
                                         int(slots), int(mark), reinterpret_cast<uint32_t*>(pos.data_ptr<int64_t>()),
                                         reinterpret_cast<uint32_t*>(neg.data_ptr<int64_t>()), cur_stream(views));
   TORCH_CHECK(n > 0, "bsi_distinct: not launched");
@@ -340,32 +363,20 @@ int64_t bsi_extract(torch::Tensor progs, torch::Tensor views, int64_t S, torch::
                     torch::Tensor values, torch::Tensor valid) {
   check_dev(progs, "progs");
   check_dev(views, "views");
-  check_dev(unit_off, "unit_off");
-  check_dev(col_base, "col_base");
-  check_dev(values, "values");
   check_dev(valid, "valid");
-  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24), "bsi_extract: shard count");
-  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  check_shards(S, 24, "bsi_extract");
+  check_filter_prog(progs);
   const pk::BsiArgs b = bsi_args_from(bsi_args);
   TORCH_CHECK(b.depth >= 0 && b.depth <= pk::EXTRACT_MAX_PLANES, "bsi_extract: bit depth");
-  TORCH_CHECK(b.view >= 0 && int64_t(b.view) < views.numel() / int64_t(sizeof(pk::ViewDev)), "bsi_extract: view slot");
-  TORCH_CHECK(unit_off.scalar_type() == torch::kInt64 && unit_off.is_contiguous() && unit_off.numel() >= S * 16,
-              "unit_off must be int64[S * 16]");
-  TORCH_CHECK(col_base.scalar_type() == torch::kInt64 && col_base.is_contiguous() && col_base.numel() >= S,
-              "col_base must be int64[S]");
+  check_view_slot(b.view, views, "bsi_extract");
+  check_i64(unit_off, S * 16, "unit_off");
+  check_i64(col_base, S, "col_base");
+  check_i64(values, 0, "values");
   const int64_t cap = values.numel();
-  TORCH_CHECK(values.scalar_type() == torch::kInt64 && values.is_contiguous(), "values must be int64[cap]");
-  TORCH_CHECK(valid.scalar_type() == torch::kUInt8 && valid.is_contiguous() && valid.numel() == cap,
-              "valid must be uint8[cap]");
-  uint64_t* cols = nullptr;
-  if (columns.numel()) {
-    check_dev(columns, "columns");
-    TORCH_CHECK(columns.scalar_type() == torch::kInt64 && columns.is_contiguous() && columns.numel() == cap,
-                "columns must be int64[cap] or empty");
-    cols = reinterpret_cast<uint64_t*>(columns.data_ptr<int64_t>());
-  }
-  const int n = pk::launch_bsi_extract(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
-                                       reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+  TORCH_CHECK(valid.scalar_type() == torch::kUInt8 && valid.numel() == cap, "valid must be uint8[cap]");
+  uint64_t* cols = columns_or_null(columns, cap, true);
+  const int n = pk::launch_bsi_extract(progs_of(progs),
+                                       views_of(views), int(S), b,
                                        int(slots), unit_off.data_ptr<int64_t>(), col_base.data_ptr<int64_t>(), base,
                                        cap, cols, values.data_ptr<int64_t>(), valid.data_ptr<uint8_t>(),
                                        cur_stream(views));
@@ -384,12 +395,11 @@ int64_t bsi_sort_select(int64_t mode, torch::Tensor progs, torch::Tensor views, 
   check_dev(progs, "progs");
   check_dev(views, "views");
   TORCH_CHECK(mode == 1 || mode == 2, "bsi_sort_select: mode");
-  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24), "bsi_sort_select: shard count");
-  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
+  check_shards(S, 24, "bsi_sort_select");
+  check_filter_prog(progs);
   const pk::BsiArgs b = bsi_args_from(bsi_args);
   TORCH_CHECK(b.depth >= 0 && b.depth <= pk::SORT_MAX_PLANES, "bsi_sort_select: bit depth");
-  TORCH_CHECK(b.view >= 0 && int64_t(b.view) < views.numel() / int64_t(sizeof(pk::ViewDev)),
-              "bsi_sort_select: view slot");
+  check_view_slot(b.view, views, "bsi_sort_select");
   TORCH_CHECK(select_all || (T > -(int64_t(1) << 32) && T < (int64_t(1) << 32)), "bsi_sort_select: threshold");
   const int64_t blocks = pk::sort_blocks(int(S), pk::sort_slots(b.depth, int(slots)));
   int32_t* cnt = nullptr;
@@ -401,14 +411,13 @@ int64_t bsi_sort_select(int64_t mode, torch::Tensor progs, torch::Tensor views, 
                 "counts must be int32[blocks * 2]");
     cnt = counts.data_ptr<int32_t>();
   } else {
-    for (const torch::Tensor* t : {&before_off, &eq_before, &m, &col_base, &columns, &values}) {
-      check_dev(*t, "bsi_sort_select tensor");
-      TORCH_CHECK(t->scalar_type() == torch::kInt64 && t->is_contiguous(), "bsi_sort_select: int64 tensors");
-    }
-    TORCH_CHECK(before_off.numel() >= blocks && eq_before.numel() >= blocks, "offsets must be int64[blocks]");
-    TORCH_CHECK(m.numel() >= 1, "m must be int64[1]");
-    TORCH_CHECK(col_base.numel() >= S, "col_base must be int64[S]");
+    check_i64(before_off, blocks, "before_off");
+    check_i64(eq_before, blocks, "eq_before");
+    check_i64(m, 1, "m");
+    check_i64(col_base, S, "col_base");
+    check_i64(values, 0, "values");
     cap = values.numel();
+    check_i64(columns, cap, "columns");
     TORCH_CHECK(columns.numel() == cap, "columns and values must have the same length");
     bo = before_off.data_ptr<int64_t>();
     eb = eq_before.data_ptr<int64_t>();
@@ -417,8 +426,8 @@ int64_t bsi_sort_select(int64_t mode, torch::Tensor progs, torch::Tensor views, 
     cols = columns.data_ptr<int64_t>();
     vals = values.data_ptr<int64_t>();
   }
-  const int n = pk::launch_bsi_sort_select(int(mode), reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
-                                           reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+  const int n = pk::launch_bsi_sort_select(int(mode), progs_of(progs),
+                                           views_of(views), int(S), b,
                                            int(slots), int(select_all), int(desc), select_all ? 0 : T, cnt, bo, eb, mp,
                                            cb, base, cap, cols, vals, cur_stream(views));
   TORCH_CHECK(n > 0, "bsi_sort_select: not launched");
@@ -435,45 +444,35 @@ int64_t rows_extract(int64_t mode, torch::Tensor progs, torch::Tensor views, int
                      torch::Tensor first) {
   check_dev(progs, "progs");
   check_dev(views, "views");
-  check_dev(unit_off, "unit_off");
-  check_dev(col_base, "col_base");
   TORCH_CHECK(mode >= 1 && mode <= 3, "rows_extract: mode 1 (count), 2 (fill) or 3 (scalar)");
-  TORCH_CHECK(S >= 0 && S < (int64_t(1) << 24) && D >= 0 && rows_per_block >= 0 && cap >= 0, "rows_extract sizes");
-  TORCH_CHECK(progs.numel() >= int64_t(sizeof(pk::QueryProg)), "one filter program required");
-  TORCH_CHECK(fview >= 0 && fview < views.numel() / int64_t(sizeof(pk::ViewDev)), "rows_extract: view slot");
-  TORCH_CHECK(unit_off.scalar_type() == torch::kInt64 && unit_off.numel() >= S * 16, "unit_off must be int64[S * 16]");
-  TORCH_CHECK(col_base.scalar_type() == torch::kInt64 && col_base.numel() >= S, "col_base must be int64[S]");
+  check_shards(S, 24, "rows_extract");
+  TORCH_CHECK(D >= 0 && rows_per_block >= 0 && cap >= 0, "rows_extract sizes");
+  check_filter_prog(progs);
+  check_view_slot(fview, views, "rows_extract");
+  check_i64(unit_off, S * 16, "unit_off");
+  check_i64(col_base, S, "col_base");
   const int64_t blocks = pk::rows_extract_blocks(int(S), D, rows_per_block);
   TORCH_CHECK(blocks >= 0, "rows_extract: grid too large");
-  uint64_t* cols = nullptr;
-  if (columns.numel()) {
-    check_dev(columns, "columns");
-    TORCH_CHECK(columns.scalar_type() == torch::kInt64 && columns.numel() >= cap, "columns must be int64[>= cap]");
-    cols = reinterpret_cast<uint64_t*>(columns.data_ptr<int64_t>());
-  }
+  uint64_t* cols = columns_or_null(columns, cap, false);
   int64_t *wgp = nullptr, *keyp = nullptr, *firstp = nullptr, *rowp = nullptr;
   int64_t T = 0;
   if (mode == 3) {
-    check_dev(row_ids, "row_ids");
-    check_dev(first, "first");
-    TORCH_CHECK(row_ids.scalar_type() == torch::kInt64 && row_ids.numel() >= D, "row_ids must be int64[D]");
-    TORCH_CHECK(first.scalar_type() == torch::kInt64 && first.numel() >= cap, "first must be int64[>= cap]");
+    check_i64(row_ids, D, "row_ids");
+    check_i64(first, cap, "first");
     rowp = row_ids.data_ptr<int64_t>();
     firstp = first.data_ptr<int64_t>();
   } else {
-    check_dev(wg, "wg");
-    TORCH_CHECK(wg.scalar_type() == torch::kInt64 && wg.numel() >= blocks, "wg must be int64[blocks]");
+    check_i64(wg, blocks, "wg");
     wgp = wg.data_ptr<int64_t>();
     if (mode == 2) {
-      check_dev(keys, "keys");
-      TORCH_CHECK(keys.scalar_type() == torch::kInt64, "keys must be int64[T]");
+      check_i64(keys, 0, "keys");
       keyp = keys.data_ptr<int64_t>();
       T = keys.numel();
     }
   }
   const int64_t n = pk::launch_rows_extract(
-      int(mode), reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()),
-      reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), int(fview), D, rows_per_block,
+      int(mode), progs_of(progs),
+      views_of(views), int(S), int(fview), D, rows_per_block,
       int(rows_per_wave < 0 || rows_per_wave > 64 ? 0 : rows_per_wave), unit_off.data_ptr<int64_t>(),
       col_base.data_ptr<int64_t>(), cap, cols, wgp, keyp, T, reinterpret_cast<const uint64_t*>(rowp),
       reinterpret_cast<uint64_t*>(firstp), cur_stream(views));
@@ -501,19 +500,10 @@ void bsi_sum(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tensor 
   check_dev(views, "views");
   check_dev(out_sum, "out_sum");
   check_dev(out_cnt, "out_cnt");
-  TORCH_CHECK(!bsi_args.is_cuda() && bsi_args.scalar_type() == torch::kInt64 && bsi_args.numel() == 67,
-              "bsi_args must be a cpu int64[67]: view, depth, exists, sign, bit_row[63]");
-  auto a = bsi_args.data_ptr<int64_t>();
-  pk::BsiArgs b{};
-  b.view = int32_t(a[0]);
-  b.depth = int32_t(a[1]);
-  TORCH_CHECK(b.depth >= 0 && b.depth <= 63, "bsi depth");
-  b.row_exists = a[2];
-  b.row_sign = a[3];
-  for (int i = 0; i < 64; i++) b.bit_row[i] = i < 63 ? a[4 + i] : -1;
+  const pk::BsiArgs b = bsi_args_from(bsi_args);
   const int Q = int(progs.numel() / sizeof(pk::QueryProg));
-  pk::launch_bsi_sum(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), Q,
-                     reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b,
+  pk::launch_bsi_sum(progs_of(progs), Q,
+                     views_of(views), int(S), b,
                      reinterpret_cast<unsigned long long*>(out_sum.data_ptr<int64_t>()),
                      reinterpret_cast<unsigned long long*>(out_cnt.data_ptr<int64_t>()), int(fmode),
                      cur_stream(progs));
@@ -527,28 +517,19 @@ int64_t bsi_group_sum(torch::Tensor progs, torch::Tensor views, int64_t S, torch
   check_dev(progs, "progs");
   check_dev(views, "views");
   check_dev(out_sum, "out_sum");
-  check_dev(out_cnt, "out_cnt");
-  TORCH_CHECK(!bsi_args.is_cuda() && bsi_args.scalar_type() == torch::kInt64 && bsi_args.numel() == 67,
-              "bsi_args must be a cpu int64[67]: view, depth, exists, sign, bit_row[63]");
   TORCH_CHECK(progs.numel() % int64_t(sizeof(pk::QueryProg)) == 0, "progs must hold whole programs");
   const int64_t G = progs.numel() / int64_t(sizeof(pk::QueryProg));
-  TORCH_CHECK(G < (int64_t(1) << 31) && S >= 0 && S < (int64_t(1) << 27), "bsi_group_sum: batch size");
-  TORCH_CHECK(out_sum.scalar_type() == torch::kInt64 && out_sum.numel() >= G, "out_sum must be int64[G]");
-  TORCH_CHECK(out_cnt.scalar_type() == torch::kInt64 && out_cnt.numel() >= G, "out_cnt must be int64[G]");
+  TORCH_CHECK(G < (int64_t(1) << 31), "bsi_group_sum: batch size");
+  check_shards(S, 27, "bsi_group_sum");
+  check_i64(out_sum, G, "out_sum");
+  check_i64(out_cnt, G, "out_cnt");
   TORCH_CHECK(views.numel() % int64_t(sizeof(pk::ViewDev)) == 0, "views must hold whole ViewDev records");
-  auto a = bsi_args.data_ptr<int64_t>();
-  pk::BsiArgs b{};
-  b.view = int32_t(a[0]);
-  b.depth = int32_t(a[1]);
-  TORCH_CHECK(b.depth >= 0 && b.depth <= 63, "bsi depth");
-  TORCH_CHECK(a[0] >= 0 && a[0] < views.numel() / int64_t(sizeof(pk::ViewDev)), "bsi view slot");
+  const pk::BsiArgs b = bsi_args_from(bsi_args);
+  check_view_slot(bsi_args.data_ptr<int64_t>()[0], views, "bsi_group_sum");
   TORCH_CHECK(planes >= 1 && planes <= 64 && gchunk >= 1 && gchunk < (int64_t(1) << 31), "bsi_group_sum: slab / chunk");
-  b.row_exists = a[2];
-  b.row_sign = a[3];
-  for (int i = 0; i < 64; i++) b.bit_row[i] = i < 63 ? a[4 + i] : -1;
   const int nslab = pk::launch_bsi_group_sum(
-      reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), int(G),
-      reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S), b, int(planes), int(gchunk),
+      progs_of(progs), int(G),
+      views_of(views), int(S), b, int(planes), int(gchunk),
       int(fmode), reinterpret_cast<unsigned long long*>(out_sum.data_ptr<int64_t>()),
       reinterpret_cast<unsigned long long*>(out_cnt.data_ptr<int64_t>()), cur_stream(progs));
   TORCH_CHECK(nslab >= 0, "bsi_group_sum: grid too large");
@@ -566,8 +547,8 @@ void and2_count(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
   const int64_t n = int64_t(Q) * S * 16;
   TORCH_CHECK(pairs.numel() * pairs.element_size() >= n * 8, "pairs scratch must hold S*16*Q uint2");
   TORCH_CHECK(partial.scalar_type() == torch::kInt32 && partial.numel() >= n, "partial must be int32[S*16*Q]");
-  pk::launch_and2_pairs(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), Q,
-                        reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S),
+  pk::launch_and2_pairs(progs_of(progs), Q,
+                        views_of(views), int(S),
                         reinterpret_cast<uint2*>(pairs.data_ptr()), partial.data_ptr<int32_t>(), int(cq),
                         int(variant), cur_stream(progs));
   check_launch("and2_pairs");
@@ -601,8 +582,8 @@ void and2_count_total(torch::Tensor progs, torch::Tensor views, int64_t S, torch
                   work.numel() >= pk::and2_work_bytes(Q) && reinterpret_cast<uintptr_t>(work.data_ptr()) % 256 == 0,
               "work must be 256-byte aligned uint8[and2_work_bytes(Q)]");
   const bool ok = pk::launch_and2_total(
-      reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), int(Q),
-      reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(V), int(S), ti.data_ptr<int64_t>(),
+      progs_of(progs), int(Q),
+      views_of(views), int(V), int(S), ti.data_ptr<int64_t>(),
       out.data_ptr<int64_t>(), out.numel(), reinterpret_cast<uint2*>(pairs.data_ptr()), partial.data_ptr<int32_t>(),
       work.data_ptr<uint8_t>(), int(cq), int(variant), cur_stream(progs));
   TORCH_CHECK(ok, "and2_count_total: no device-count pair kernel for ", Q, " queries, cq ", cq, ", variant ",
@@ -1188,8 +1169,8 @@ void expr_dense(torch::Tensor progs, torch::Tensor views, int64_t S, torch::Tens
               "outp int16[Q*S*16*4096]");
   TORCH_CHECK(out_meta.scalar_type() == torch::kInt64 && out_meta.numel() >= int64_t(Q) * S * 16,
               "out_meta int64[Q*S*16]");
-  pk::launch_expr_dense(reinterpret_cast<const pk::QueryProg*>(progs.data_ptr<uint8_t>()), Q,
-                        reinterpret_cast<const pk::ViewDev*>(views.data_ptr<uint8_t>()), int(S),
+  pk::launch_expr_dense(progs_of(progs), Q,
+                        views_of(views), int(S),
                         reinterpret_cast<uint16_t*>(outp.data_ptr<int16_t>()), out_meta.data_ptr<int64_t>(),
                         cur_stream(progs));
   check_launch("expr_dense");

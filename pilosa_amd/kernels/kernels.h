@@ -146,17 +146,38 @@ int launch_bsi_group_sum(const QueryProg* progs, int G, const ViewDev* views, in
                          int gchunk, int fmode, unsigned long long* out_sum, unsigned long long* out_cnt,
                          hipStream_t st);
 
+// The slab kernels K26 / K27 / K29 below (bsi_slab.h): one workgroup per (arena
+// shard, key, slice of n tile slots), the slice staged into fixed_tiles + depth
+// LDS tiles of n KiB next to the four WaveScratch.  slab_slots() = the tile
+// slots per workgroup: the largest of 8, 4, 2, 1 that fits the CU's 160 KiB at
+// this depth, or want rounded down to a power of two where that is smaller
+// (want < 1: no wish).
+constexpr int64_t SLAB_STATIC_LDS = 40960;  // four WaveScratch (bsi_slab.h asserts it)
+inline int slab_slots(int fixed_tiles, int depth, int want) {
+  int n = 8;
+  while (n > 1 && SLAB_STATIC_LDS + int64_t(fixed_tiles + depth) * n * 1024 > 160 * 1024) n >>= 1;
+  if (want >= 1 && want < n) {
+    int w = 1;
+    while (w * 2 <= want) w <<= 1;  // round down to a power of two
+    n = w;
+  }
+  return n;
+}
+inline int64_t slab_blocks(int S, int n) { return int64_t(S) * 16 * (8 / n); }
+inline int slab_lds_bytes(int fixed_tiles, int depth, int n) { return (fixed_tiles + depth) * n * 1024; }
+
 // Distinct(field=) (distinct_kernels.hip, K26): bit v of pos / neg |= 1 for
 // every column of exists & filter (progs[0]; nprog == 0: no filter) holding the
 // base-relative value +v / -v; pos and neg hold 2^depth bits each (at least one
 // 32-bit word), zeroed by the caller.  depth <= DISTINCT_MAX_PLANES.  slots =
 // tile slots per workgroup (1, 2, 4 or 8; anything else: the largest that
-// fits), clamped by distinct_slots() to what the 160 KiB of LDS hold at this
-// depth.  mark: 0 always OR, 1 test the bit first, 2 also skip a repeat of the
+// fits), clamped by distinct_slots() = slab_slots() to what the 160 KiB of LDS
+// hold at this depth.  mark: 0 always OR, 1 test the bit first, 2 also skip a repeat of the
 // thread's previous value.  Returns the slots used, -1 when nothing was launched
 // (depth out of range, grid too large).
 constexpr int DISTINCT_MAX_PLANES = 32;
-int distinct_slots(int depth, int want);
+constexpr int DISTINCT_FIXED_TILES = 2;  // consider, sign
+inline int distinct_slots(int depth, int want) { return slab_slots(DISTINCT_FIXED_TILES, depth, want); }
 int launch_bsi_distinct(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots, int mark,
                         uint32_t* pos, uint32_t* neg, hipStream_t st);
 
@@ -171,7 +192,8 @@ int launch_bsi_distinct(const QueryProg* progs, const ViewDev* views, int S, Bsi
 // depth <= EXTRACT_MAX_PLANES.  slots as for launch_bsi_distinct, clamped by
 // extract_slots().  Returns the slots used, -1 when nothing was launched.
 constexpr int EXTRACT_MAX_PLANES = 32;
-int extract_slots(int depth, int want);
+constexpr int EXTRACT_FIXED_TILES = 3;  // consider, exists, sign
+inline int extract_slots(int depth, int want) { return slab_slots(EXTRACT_FIXED_TILES, depth, want); }
 int launch_bsi_extract(const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots,
                        const int64_t* unit_off, const int64_t* col_base, int64_t base, int64_t cap, uint64_t* columns,
                        int64_t* values, uint8_t* valid, hipStream_t st);
@@ -196,8 +218,9 @@ int launch_bsi_extract(const QueryProg* progs, const ViewDev* views, int S, BsiA
 // clamped by sort_slots().  Returns the slots used, -1 when nothing was
 // launched.
 constexpr int SORT_MAX_PLANES = 32;
-int sort_slots(int depth, int want);
-int64_t sort_blocks(int S, int n);
+constexpr int SORT_FIXED_TILES = 2;  // consider, sign
+inline int sort_slots(int depth, int want) { return slab_slots(SORT_FIXED_TILES, depth, want); }
+inline int64_t sort_blocks(int S, int n) { return slab_blocks(S, n); }
 int launch_bsi_sort_select(int mode, const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots,
                            int select_all, int desc, int64_t T, int32_t* counts, const int64_t* before_off,
                            const int64_t* eq_before, const int64_t* m, const int64_t* col_base, int64_t base,

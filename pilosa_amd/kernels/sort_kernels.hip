@@ -25,16 +25,16 @@
 //     atomics on the output, no grid-wide barrier, no spin, no cooperative
 //     launch.
 //
-// Work unit, stages 1 and 2 as in K26 / K27: one workgroup of four waves owns
-// one (arena shard, key, slice); a slice is n of the key's 8 tile slots (8192
-// columns each; n is 1, 2, 4 or 8).
+// Work unit, slab layout, stages 1 and 2 and the block scans are those of
+// bsi_slab.h, shared with K26 and K27: one workgroup of four waves owns one
+// (arena shard, key, slice of n tile slots).
 //
-//   1. Every wave evaluates the slice of consider = exists & filter.  A key
-//      without an exists container, or an empty slice, ends the workgroup
-//      here, block-uniformly, before any barrier (its count pair stays 0).
-//   2. Staging: the sign row and the planes go round-robin over the waves into
-//      the block-shared LDS slab ([tile][slot][lane], 16 bytes per lane;
-//      slice_each, bsi_tile.h).  One __syncthreads().
+//   1. Every wave evaluates the slice of consider = exists & filter
+//      (slab_consider).  A key without an exists container, or an empty slice,
+//      ends the workgroup here, block-uniformly, before any barrier (its count
+//      pair stays 0).
+//   2. Staging (slab_stage): the sign row and the planes go round-robin over
+//      the waves into the slab.  One __syncthreads().
 //   3. Compare: thread tid owns 32-column word tid of each slot and runs the
 //      bit-sliced comparator (sort_select.h) MSB first over the staged plane
 //      words: a `before` word and an `equal` word, no transpose.  select_all
@@ -49,8 +49,7 @@
 //      the two launches cannot write outside them; the caller initialises the
 //      column vector to -1, so a slot the fill did not reach is recognisable.
 //
-// LDS: four WaveScratch (40 KiB, static) + (2 + depth) * n KiB dynamic
-// (consider, sign, planes); the launcher clamps n to what fits 160 KiB.
+// Slab: SORT_FIXED_TILES + depth tiles (consider, sign, planes).
 //
 // Resource usage (hipcc -O3 --offload-arch=gfx950
 // -Rpass-analysis=kernel-resource-usage), see profiles/sort/resource_usage.txt:
@@ -65,6 +64,7 @@
 #include "expr_tile.h"
 #include "bsi_tile.h"
 #include "bit_transpose.h"
+#include "bsi_slab.h"
 #include "sort_select.h"
 
 namespace pk {
@@ -76,59 +76,32 @@ __global__ __launch_bounds__(256) void bsi_sort_select_kernel(
     const int64_t* __restrict__ col_base, int64_t base, int64_t cap, int64_t* __restrict__ columns,
     int64_t* __restrict__ values) {
   __shared__ WaveScratch scratch[WAVES_PER_BLOCK];
-  extern __shared__ dq_u64x2 so_slab[];  // [2 + depth][n][64]: consider, sign, planes; slots of the slice
-  const uint32_t unit = xcd_remap(blockIdx.x, gridDim.x);
   const int wave = threadIdx.x >> 6;
   const int lane = wave_lane();
-  const uint32_t nsl = 8u / uint32_t(n);
-  const int slot0 = int(unit % nsl) * n;
-  const int j = int((unit / nsl) & 15);
-  const int s = int(unit / (nsl * 16));
+  const SlabUnit u = slab_unit(n);
+  const uint32_t unit = u.unit;
+  const int s = u.s, j = u.j, slot0 = u.slot0;
   if (s >= S) return;
   const ViewDev& bv = views[bsi.view];
   WaveScratch& ws = scratch[wave];
   BsiCtx c{bsi, bv, s, j, bv.shard_base[s], bv.rowptr + int64_t(s) * (bv.D + 1), ws.lb};
   const int depth = bsi.depth;  // <= 32 (launcher)
 
-  // ---- 1. consider slice, in every wave (block-uniform exits, no barrier yet)
+  // ---- 1. consider slice, in every wave (block-uniform exits, no barrier yet: see bsi_slab.h)
   const int64_t ce = bsi_find(c, bsi.row_exists);
   if (ce < 0) return;
-  const QueryProg& qp = progs[0];
-  uint64_t any = 0;
-  if (qp.nprog) {
-    uint32_t mask[MAXLEAF];
-    build_slots(qp, views, s, ws, mask);
-    if (!((candidate_mask(qp, mask) >> j) & 1)) return;
-    Tile f;
-    eval_tile(qp, views, s, j, ws, f);
-    slice_each(bv.payload, bv.meta[ce], ws.lb, slot0, n, [&](int i, ulong2 e) {
-      const dq_u64x2 v{e.x & f.w[i].x, e.y & f.w[i].y};
-      any |= v.x | v.y;
-      if (wave == 0) so_slab[(i - slot0) * 64 + lane] = v;
-    });
-  } else {
-    slice_each(bv.payload, bv.meta[ce], ws.lb, slot0, n, [&](int i, ulong2 e) {
-      any |= e.x | e.y;
-      if (wave == 0) so_slab[(i - slot0) * 64 + lane] = dq_u64x2{e.x, e.y};
-    });
-  }
-  if (!__ballot(any != 0)) return;
+  if (!slab_consider(progs[0], views, bv, ce, s, j, ws, slot0, n, wave, lane)) return;
 
-  // ---- 2. staging: tile 1 = sign, tile 2 + p = plane p, round-robin over the waves
+  // ---- 2. staging: tile 1 = sign, tile 2 + p = plane p
   const int64_t cs = bsi_find(c, bsi.row_sign);
   plane_index(c);
-  const uint64_t present = __ballot(c.planes >= 0) & ((1ull << depth) - 1);  // (depth <= 32)
-  for (int t = 1 + wave; t < 2 + depth; t += WAVES_PER_BLOCK) {
-    const int64_t ci = t == 1 ? cs : rl_i64(c.planes, t - 2);
-    if (ci < 0) continue;  // absent: never read back
-    dq_u64x2* dst = so_slab + t * n * 64 + lane;
-    slice_each(bv.payload, bv.meta[ci], ws.lb, slot0, n,
-               [&](int i, ulong2 e) { dst[(i - slot0) * 64] = dq_u64x2{e.x, e.y}; });
-  }
+  const uint64_t present = slab_present(c, depth);
+  slab_stage(bv, ws, slot0, n, wave, lane, SORT_FIXED_TILES + depth,
+             [&](int t) { return t == 1 ? cs : rl_i64(c.planes, t - 2); });
   __syncthreads();
 
   // ---- 3. compare: thread tid owns 32-column word tid of each slot
-  uint32_t* s32 = reinterpret_cast<uint32_t*>(so_slab);
+  uint32_t* s32 = reinterpret_cast<uint32_t*>(bsi_slab);
   int* part = reinterpret_cast<int*>(scratch[0].lb);  // wave totals (wave 0's lb is free after the barrier)
   const int tid = threadIdx.x;
   auto compare = [&](int k, uint32_t cw) -> SortWords {
@@ -181,8 +154,7 @@ __global__ __launch_bounds__(256) void bsi_sort_select_kernel(
     if (cw) r = compare(k, cw);
     eqs[k * 256 + tid] = r.equal;
     s32[k * 256 + tid] = r.before;
-    const int incl = wave_scan_incl(__popc(r.equal));
-    if (lane == 63) part_eq[k * WAVES_PER_BLOCK + wave] = incl;
+    slab_scan_totals(part_eq, k, wave, lane, __popc(r.equal));
   }
   __syncthreads();
 
@@ -193,19 +165,12 @@ __global__ __launch_bounds__(256) void bsi_sort_select_kernel(
   for (int k = 0; k < n; k++) {
     const uint32_t ew = eqs[k * 256 + tid];
     const int ec = __popc(ew);
-    int64_t prior = eq_run + (wave_scan_incl(ec) - ec);
-#pragma unroll
-    for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-      const int p = part_eq[k * WAVES_PER_BLOCK + w];
-      if (w < wave) prior += p;
-      eq_run += p;
-    }
+    const int64_t prior = slab_scan_pos(part_eq, k, wave, ec, eq_run);
     const int64_t left = m - prior;
     const int q = left <= 0 ? 0 : left >= ec ? ec : int(left);
     const uint32_t sel = s32[k * 256 + tid] | (q == ec ? ew : first_set_bits32(ew, q));
     s32[k * 256 + tid] = sel;
-    const int incl = wave_scan_incl(__popc(sel));
-    if (lane == 63) part_sel[k * WAVES_PER_BLOCK + wave] = incl;
+    slab_scan_totals(part_sel, k, wave, lane, __popc(sel));
   }
   __syncthreads();
 
@@ -214,20 +179,13 @@ __global__ __launch_bounds__(256) void bsi_sort_select_kernel(
   int64_t run = before_off[unit] + (eqb < m ? eqb : (m > 0 ? m : 0));  // output position of the slot's first column
   for (int k = 0; k < n; k++) {
     const uint32_t sel = s32[k * 256 + tid];
-    const int cnt = __popc(sel);
-    int64_t o = run + (wave_scan_incl(cnt) - cnt);
-#pragma unroll
-    for (int w = 0; w < WAVES_PER_BLOCK; w++) {
-      const int p = part_sel[k * WAVES_PER_BLOCK + w];
-      if (w < wave) o += p;
-      run += p;
-    }
+    int64_t o = slab_scan_pos(part_sel, k, wave, __popc(sel), run);
     if (sel) {
       const uint32_t sw = cs >= 0 ? s32[(n + k) * 256 + tid] : 0u;
       uint32_t a[32];
 #pragma unroll
       for (int p = 0; p < 32; p++)
-        a[p] = (p < depth && ((present >> p) & 1)) ? s32[((2 + p) * n + k) * 256 + tid] : 0u;
+        a[p] = (p < depth && ((present >> p) & 1)) ? s32[((SORT_FIXED_TILES + p) * n + k) * 256 + tid] : 0u;
       bit_transpose32(a);
       const uint64_t colk = col0 + uint64_t(slot0 + k) * 8192u;
 #pragma unroll
@@ -246,20 +204,6 @@ __global__ __launch_bounds__(256) void bsi_sort_select_kernel(
 
 // ------------------------------------------------------------ launcher
 
-int sort_slots(int depth, int want) {
-  int n = 8;
-  // four WaveScratch + (consider, sign, planes) * n KiB inside the CU's 160 KiB
-  while (n > 1 && int64_t(sizeof(WaveScratch)) * WAVES_PER_BLOCK + int64_t(2 + depth) * n * 1024 > 160 * 1024) n >>= 1;
-  if (want >= 1 && want < n) {
-    int w = 1;
-    while (w * 2 <= want) w <<= 1;  // round down to a power of two
-    n = w;
-  }
-  return n;
-}
-
-int64_t sort_blocks(int S, int n) { return int64_t(S) * 16 * (8 / n); }
-
 int launch_bsi_sort_select(int mode, const QueryProg* progs, const ViewDev* views, int S, BsiArgs bsi, int slots,
                            int select_all, int desc, int64_t T, int32_t* counts, const int64_t* before_off,
                            const int64_t* eq_before, const int64_t* m, const int64_t* col_base, int64_t base,
@@ -271,12 +215,9 @@ int launch_bsi_sort_select(int mode, const QueryProg* progs, const ViewDev* view
   if (S <= 0 || (mode == 2 && cap == 0)) return n;
   const int64_t blocks = sort_blocks(S, n);
   if (blocks >= (int64_t(1) << 30)) return -1;
-  const int lds = (2 + bsi.depth) * n * 1024;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bsi_sort_select_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  hipLaunchKernelGGL(bsi_sort_select_kernel, dim3(unsigned(blocks)), dim3(64 * WAVES_PER_BLOCK), lds, st, progs, views,
-                     S, bsi, n, mode, select_all, desc, int(T < 0), uint32_t(mag), counts, before_off, eq_before, m,
-                     col_base, base, cap, columns, values);
+  slab_launch(bsi_sort_select_kernel, blocks, slab_lds_bytes(SORT_FIXED_TILES, bsi.depth, n), st, progs, views, S, bsi,
+              n, mode, select_all, desc, int(T < 0), uint32_t(mag), counts, before_off, eq_before, m, col_base, base, cap,
+              columns, values);
   return n;
 }
 

@@ -62,6 +62,11 @@ _hot_lock = threading.Lock()
 _D2H_POLL = float(os.environ.get("PILOSA_D2H_POLL", "0"))
 
 
+def _env_int(name: str, default: int) -> int:
+    """a PILOSA_* integer knob read per call; unset or empty = ``default``"""
+    return int(os.environ.get(name) or default)
+
+
 def kernels():
     """Load the in-tree HIP extension; fail loudly when it is missing."""
     global _ext
@@ -2053,27 +2058,59 @@ class GpuEngine:
         return int(v), int(c), bool(found)
 
     @staticmethod
-    def _bsi_filter_program(filt: Optional[object], bsi_view: "DeviceView"):
-        """(one packed filter program -- the empty one for ``filt`` None --, its
-        views in slot order with the BSI view in slot 0) of a filtered BSI
-        aggregate (Min / Max, Percentile)."""
+    def _bsi_filter_program(filters: Sequence[Optional[object]], bsi_view: "DeviceView"):
+        """(the packed filter programs, one per entry of ``filters`` -- the
+        empty one for None --, their views in slot order with the BSI view in
+        slot 0) of a filtered BSI call (Sum, Min / Max, Percentile, ...)."""
         view_index: Dict[int, int] = {id(bsi_view): 0}
         views = {id(bsi_view): bsi_view}
-        if filt is not None:
-            def collect(node):
-                if isinstance(node, Leaf):
-                    views[id(node.view)] = node.view
-                elif isinstance(node, Op):
-                    for a in node.args:
-                        collect(a)
-            collect(filt)
-            progs = pack_programs([compile_expr(filt, view_index)])
-        else:
-            progs = pack_programs([([], [], [])])
+
+        def collect(node):
+            if isinstance(node, Leaf):
+                views[id(node.view)] = node.view
+            elif isinstance(node, Op):
+                for a in node.args:
+                    collect(a)
+
+        compiled = []
+        for f in filters:
+            if f is None:
+                compiled.append(([], [], []))
+                continue
+            collect(f)
+            compiled.append(compile_expr(f, view_index))
         ordered = [None] * len(view_index)
         for vid, slot in view_index.items():
             ordered[slot] = views[vid]
-        return progs, ordered
+        return pack_programs(compiled), ordered
+
+    def _upload_filter(self, filt: Optional[object], view: "DeviceView"):
+        """One filter's program with ``view`` in slot 0, uploaded: (the host
+        program, device programs, device views)."""
+        progs, ordered = self._bsi_filter_program([filt], view)
+        return (progs, *self.upload_batch(progs, ordered))
+
+    def _bsi_call(self, filt: Optional[object], bsi_view: "DeviceView", depth: int):
+        """The common setup of a filtered BSI call: (device programs, device
+        views, the host bsi_args tensor) after one upload_batch, or None -- and
+        no upload -- when there is no shard or the field has no exists row."""
+        progs, ordered = self._bsi_filter_program([filt], bsi_view)
+        args = self.bsi_args(bsi_view, depth)
+        if not bsi_view.S or args[2] < 0:
+            return None
+        tp, tv = self.upload_batch(progs, ordered)
+        return tp, tv, self.torch.from_numpy(args)
+
+    def _col_base(self, view: "DeviceView"):
+        """int64[S] on the device: the global column id of column 0 of every arena shard"""
+        from pilosa_amd import shardwidth
+        return self.torch.from_numpy(np.asarray(view.shards, dtype=np.int64) * shardwidth.ARENA_WIDTH).to(self.device)
+
+    def _exclusive_offsets(self, counts):
+        """(inclusive, exclusive) int64 prefix sums of ``counts`` along axis 0, on the device"""
+        c64 = counts.to(self.torch.int64)
+        ends = self.torch.cumsum(c64, 0)
+        return ends, ends - c64
 
     def bsi_kth(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, num: int = 0,
                 den: int = 1, rank=None):
@@ -2098,18 +2135,16 @@ class GpuEngine:
         each until they return."""
         torch = self.torch
         S = bsi_view.S
-        progs, ordered = self._bsi_filter_program(filt, bsi_view)
-        args = self.bsi_args(bsi_view, depth)
-        if not S or args[2] < 0:
+        up = self._bsi_call(filt, bsi_view, depth)
+        if up is None:
             return None if rank is None else (0, None, 0, None)
+        tp, tv, targs = up
         cand = torch.empty(S * 16 * 1024, dtype=torch.int64, device=self.device)
         cnt = torch.zeros(66, dtype=torch.int64, device=self.device)
-        tp, tv = self.upload_batch(progs, ordered)
-        targs = torch.from_numpy(args)
         self.ext.bsi_kth_init(tp, tv, S, targs, cand, cnt)
         n, nneg = (int(x) for x in self.to_host(cnt[:2]).tolist())
         if n <= 0:
-            return None if rank is None else (0, None, 0, (tp, tv, targs))
+            return None if rank is None else (0, None, 0, up)
         from pilosa_amd.executor import nearest_rank
         from .bsi import kth_plan
         if rank is None:
@@ -2117,7 +2152,7 @@ class GpuEngine:
         else:
             k = rank(n)
             if k is None:
-                return n, None, 0, (tp, tv, targs)
+                return n, None, 0, up
         largest, r, tot = kth_plan(k, n, nneg)
         largest = int(largest)
         if depth > 0:
@@ -2129,7 +2164,7 @@ class GpuEngine:
         value = -int(mag) if largest else int(mag)
         if rank is None:
             return value, int(count)
-        return n, value, int(count), (tp, tv, targs)
+        return n, value, int(count), up
 
     # bit planes bsi_sort_select_kernel compares and transposes at most (kernels.h SORT_MAX_PLANES)
     SORT_MAX_PLANES = 32
@@ -2169,7 +2204,6 @@ class GpuEngine:
         sort's temporaries, from torch's caching allocator, outside the
         arenas' ``hbm_budget``."""
         torch = self.torch
-        from pilosa_amd import shardwidth
         none = (np.zeros(0, np.uint64), np.zeros(0, np.int64))
         if depth < 0 or depth > self.SORT_MAX_PLANES:
             raise NotImplementedError("bit depth beyond the transpose")
@@ -2199,12 +2233,9 @@ class GpuEngine:
         select_all = T is None
         self.ext.bsi_sort_select(1, tp, tv, S, targs, n_slots, select_all, bool(desc), int(T or 0), counts,
                                  e64, e64, e64, e64, 0, e64, e64)
-        c64 = counts.view(blocks, 2).to(torch.int64)
-        ends = torch.cumsum(c64, 0)
-        offs = ends - c64
+        ends, offs = self._exclusive_offsets(counts.view(blocks, 2))
         m = (k - ends[-1, 0]).clamp(min=0).reshape(1).contiguous()
-        col_base = torch.from_numpy(np.asarray(bsi_view.shards, dtype=np.int64) *
-                                    shardwidth.ARENA_WIDTH).to(self.device)
+        col_base = self._col_base(bsi_view)
         columns = torch.full((k,), -1, dtype=torch.int64, device=self.device)
         info = torch.iinfo(torch.int64)
         values = torch.full((k,), info.min if desc else info.max, dtype=torch.int64, device=self.device)
@@ -2242,14 +2273,13 @@ class GpuEngine:
         S = bsi_view.S
         if depth < 0 or depth > self.DISTINCT_MAX_PLANES:
             raise NotImplementedError("bit depth beyond the transpose")
-        progs, ordered = self._bsi_filter_program(filt, bsi_view)
-        args = self.bsi_args(bsi_view, depth)
-        if not S or args[2] < 0:
+        up = self._bsi_call(filt, bsi_view, depth)
+        if up is None:
             return empty, empty
+        tp, tv, targs = up
         words = max(1, (1 << depth) >> 6)
         bm = torch.zeros(2 * words, dtype=torch.int64, device=self.device)
-        tp, tv = self.upload_batch(progs, ordered)
-        self.ext.bsi_distinct(tp, tv, S, torch.from_numpy(args), int(slots), int(mark), bm[:words], bm[words:])
+        self.ext.bsi_distinct(tp, tv, S, targs, int(slots), int(mark), bm[:words], bm[words:])
         nz = torch.nonzero(bm).reshape(-1)
         both = self.to_host(torch.stack([nz, bm[nz]])).numpy()
         idx, w = both[0], both[1].view(np.uint64)
@@ -2303,7 +2333,6 @@ class GpuEngine:
         field next to the sort's temporaries, from torch's caching allocator,
         per request, outside the arenas' ``hbm_budget``."""
         torch = self.torch
-        from pilosa_amd import shardwidth
         bv0 = fields[0][0] if fields else rows[0][0]
         S = bv0.S
         for bv, depth, _ in fields:
@@ -2319,15 +2348,12 @@ class GpuEngine:
                 [ExtractedTable.null_vector(typ, 0) for _, typ in rows], 0)
         if not S:
             return none
-        progs, ordered = self._bsi_filter_program(filt, bv0)
-        tp, tv = self.upload_batch(progs, ordered)
+        progs, tp, tv = self._upload_filter(filt, bv0)
         counts = torch.zeros(S * 16, dtype=torch.int32, device=self.device)
         self.ext.expr_count(tp, tv, S, torch.empty(0, dtype=torch.int64, device=self.device), counts,
                             2 if bool(flat_mask(progs).all()) else 0)
-        c64 = counts.to(torch.int64)
-        ends = torch.cumsum(c64, 0)
-        offs = ends - c64
-        live = c64 > 0
+        ends, offs = self._exclusive_offsets(counts)
+        live = counts > 0
         if window is not None:
             live = live & (offs < int(window))
         last = torch.where(live, ends, torch.zeros_like(ends)).max()
@@ -2337,14 +2363,13 @@ class GpuEngine:
         if not n_out:
             return none[0], none[1], int(total)
         unit_off = torch.where(live, offs, torch.full_like(offs, -1)).contiguous()
-        col_base = torch.from_numpy(np.asarray(bv0.shards, dtype=np.int64) * shardwidth.ARENA_WIDTH).to(self.device)
+        col_base = self._col_base(bv0)
         keep = n_out if window is None else min(n_out, int(window))
         columns = torch.empty(n_out, dtype=torch.int64, device=self.device)
         out = []
         for i, (bv, depth, base) in enumerate(fields):
             if i:
-                progs, ordered = self._bsi_filter_program(filt, bv)
-                tp, tv = self.upload_batch(progs, ordered)
+                _, tp, tv = self._upload_filter(filt, bv)
             values = torch.empty(n_out, dtype=torch.int64, device=self.device)
             valid = torch.empty(n_out, dtype=torch.uint8, device=self.device)
             self.ext.bsi_extract(tp, tv, S, torch.from_numpy(self.bsi_args(bv, depth)), int(slots), unit_off, col_base,
@@ -2371,10 +2396,9 @@ class GpuEngine:
         from pilosa_amd.models.fragment import TRUE_ROW_ID
         S, D = view.S, view.D
         view.ensure_keymask()
-        progs, ordered = self._bsi_filter_program(filt, view)   # the field's view in slot 0
-        tp, tv = self.upload_batch(progs, ordered)
-        rpb = max(0, int(os.environ.get("PILOSA_EXTRACT_ROWS_PER_BLOCK") or self.EXTRACT_ROWS_PER_BLOCK))
-        rpw = int(os.environ.get("PILOSA_EXTRACT_ROWS_PER_WAVE") or 0)
+        _, tp, tv = self._upload_filter(filt, view)   # the field's view in slot 0
+        rpb = max(0, _env_int("PILOSA_EXTRACT_ROWS_PER_BLOCK", self.EXTRACT_ROWS_PER_BLOCK))
+        rpw = _env_int("PILOSA_EXTRACT_ROWS_PER_WAVE", 0)
         none64 = torch.empty(0, dtype=torch.int64, device=self.device)
         rows_t = self._rows_tensor(view)
 
@@ -2404,7 +2428,7 @@ class GpuEngine:
         wg_end = torch.cumsum(wg, 0)
         T = int(self.to_host(wg_end[-1:]).item())
         try:
-            cap_t = int(os.environ.get("PILOSA_EXTRACT_ROWS_MAX_ENTRIES") or self.EXTRACT_ROWS_MAX_ENTRIES)
+            cap_t = _env_int("PILOSA_EXTRACT_ROWS_MAX_ENTRIES", self.EXTRACT_ROWS_MAX_ENTRIES)
         except ValueError:
             cap_t = self.EXTRACT_ROWS_MAX_ENTRIES
         if T > cap_t:
@@ -2429,12 +2453,11 @@ class GpuEngine:
     def _bsi_minmax_dev(self, filt: Optional[object], bsi_view: "DeviceView", depth: int, which: str = ""):
         torch = self.torch
         S = bsi_view.S
-        progs, ordered = self._bsi_filter_program(filt, bsi_view)
+        up = self._bsi_call(filt, bsi_view, depth)
         out = torch.zeros(S * 16 * 10, dtype=torch.int64, device=self.device)
-        args = self.bsi_args(bsi_view, depth)
-        if S and args[2] >= 0:
-            tp, tv = self.upload_batch(progs, ordered)
-            self.ext.bsi_minmax(tp, tv, S, torch.from_numpy(args), out, {"min": 1, "max": 2}.get(which, 0))
+        if up is not None:
+            tp, tv, targs = up
+            self.ext.bsi_minmax(tp, tv, S, targs, out, {"min": 1, "max": 2}.get(which, 0))
         return out
 
     def bsi_sum_async(self, filters: Sequence[Optional[object]], bsi_view: "DeviceView", depth: int,
@@ -2466,28 +2489,7 @@ class GpuEngine:
                 return bsi_sum_matrix(self, filters, bsi_view, depth)
             except CompileError:
                 pass  # a filter the dense evaluator cannot take: per-filter kernel
-        exprs = [f for f in filters if f is not None]
-        view_index: Dict[int, int] = {id(bsi_view): 0}
-        views = {id(bsi_view): bsi_view}
-
-        def collect(node):
-            if isinstance(node, Leaf):
-                views[id(node.view)] = node.view
-            elif isinstance(node, Op):
-                for a in node.args:
-                    collect(a)
-
-        compiled = []
-        for f in filters:
-            if f is None:
-                compiled.append(([], [], []))
-                continue
-            collect(f)
-            compiled.append(compile_expr(f, view_index))
-        progs = pack_programs(compiled)
-        ordered = [None] * len(view_index)
-        for vid, slot in view_index.items():
-            ordered[slot] = views[vid]
+        progs, ordered = self._bsi_filter_program(filters, bsi_view)
         args = self.bsi_args(bsi_view, depth)
         outs = torch.zeros(2 * len(filters), dtype=torch.int64, device=self.device)
         out_sum, out_cnt = outs[:len(filters)], outs[len(filters):]
@@ -2534,8 +2536,8 @@ class GpuEngine:
         args = self.bsi_args(bsi_view, depth, slot)
         if not G or not S or args[2] < 0:
             return out_sum, out_cnt
-        planes = int(os.environ.get("PILOSA_GROUPSUM_SLAB") or self.GROUPSUM_SLAB)
-        gchunk = int(os.environ.get("PILOSA_GROUPSUM_CHUNK") or self.GROUPSUM_CHUNK)
+        planes = _env_int("PILOSA_GROUPSUM_SLAB", self.GROUPSUM_SLAB)
+        gchunk = _env_int("PILOSA_GROUPSUM_CHUNK", self.GROUPSUM_CHUNK)
         nprog = progs["nprog"]
         fmode = 1 if bool(((nprog <= 1) | flat_mask(progs)).all()) else 2
         tp, tv = self.upload_batch(progs, ordered)
@@ -2563,7 +2565,7 @@ class GpuEngine:
         out = torch.zeros(view.D, dtype=torch.int64, device=self.device)
         if not view.D or not view.S:
             return out
-        rpb = int(os.environ.get("PILOSA_TOPK_ROWS_PER_BLOCK") or self.TOPK_ROWS_PER_BLOCK)
+        rpb = _env_int("PILOSA_TOPK_ROWS_PER_BLOCK", self.TOPK_ROWS_PER_BLOCK)
         if filt is None:
             self.ext.row_filter_counts(view.viewdev_tensor(), torch.zeros(0, dtype=torch.uint8), -1, view.S, out, 0)
             return out
@@ -2574,6 +2576,6 @@ class GpuEngine:
         if xd < 0:
             return out
         view.ensure_keymask()
-        rpw = int(os.environ.get("PILOSA_TOPK_ROWS_PER_WAVE") or 0)
+        rpw = _env_int("PILOSA_TOPK_ROWS_PER_WAVE", 0)
         self.ext.row_filter_counts(view.viewdev_tensor(), fv.viewdev_tensor(), xd, view.S, out, max(0, rpb), rpw)
         return out

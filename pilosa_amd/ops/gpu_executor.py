@@ -99,15 +99,20 @@ def distinct_max_depth() -> int:
 DISTINCT_SLOTS_DEFAULT = 1
 
 
-def distinct_slots_env() -> int:
-    """PILOSA_DISTINCT_SLOTS: tile slots per workgroup of bsi_distinct_kernel
-    (1, 2, 4 or 8, clamped by the launcher to what fits the LDS at the field's
-    depth); anything else means DISTINCT_SLOTS_DEFAULT."""
+def _slots_env(name: str, default: int) -> int:
+    """The tile slots per workgroup of a slab kernel from the environment: 1,
+    2, 4 or 8 (clamped by the launcher to what fits the LDS at the field's
+    depth); unset or anything else means ``default``."""
     try:
-        v = int(os.environ.get("PILOSA_DISTINCT_SLOTS", "") or DISTINCT_SLOTS_DEFAULT)
+        v = int(os.environ.get(name, "") or default)
     except ValueError:
-        return DISTINCT_SLOTS_DEFAULT
-    return v if v in (1, 2, 4, 8) else DISTINCT_SLOTS_DEFAULT
+        return default
+    return v if v in (1, 2, 4, 8) else default
+
+
+def distinct_slots_env() -> int:
+    """PILOSA_DISTINCT_SLOTS: tile slots per workgroup of bsi_distinct_kernel"""
+    return _slots_env("PILOSA_DISTINCT_SLOTS", DISTINCT_SLOTS_DEFAULT)
 
 
 # tile slots per workgroup of bsi_extract_kernel: the default is the fastest
@@ -116,14 +121,8 @@ EXTRACT_SLOTS_DEFAULT = 1
 
 
 def extract_slots_env() -> int:
-    """PILOSA_EXTRACT_SLOTS: tile slots per workgroup of bsi_extract_kernel
-    (1, 2, 4 or 8, clamped by the launcher to what fits the LDS at the field's
-    depth); anything else means EXTRACT_SLOTS_DEFAULT."""
-    try:
-        v = int(os.environ.get("PILOSA_EXTRACT_SLOTS", "") or EXTRACT_SLOTS_DEFAULT)
-    except ValueError:
-        return EXTRACT_SLOTS_DEFAULT
-    return v if v in (1, 2, 4, 8) else EXTRACT_SLOTS_DEFAULT
+    """PILOSA_EXTRACT_SLOTS: tile slots per workgroup of bsi_extract_kernel"""
+    return _slots_env("PILOSA_EXTRACT_SLOTS", EXTRACT_SLOTS_DEFAULT)
 
 
 # tile slots per workgroup of bsi_sort_select_kernel: 4 measured 9% faster under a
@@ -133,14 +132,8 @@ SORT_SLOTS_DEFAULT = 1
 
 
 def sort_slots_env() -> int:
-    """PILOSA_SORT_SLOTS: tile slots per workgroup of bsi_sort_select_kernel
-    (1, 2, 4 or 8, clamped by the launcher to what fits the LDS at the field's
-    depth); anything else means SORT_SLOTS_DEFAULT."""
-    try:
-        v = int(os.environ.get("PILOSA_SORT_SLOTS", "") or SORT_SLOTS_DEFAULT)
-    except ValueError:
-        return SORT_SLOTS_DEFAULT
-    return v if v in (1, 2, 4, 8) else SORT_SLOTS_DEFAULT
+    """PILOSA_SORT_SLOTS: tile slots per workgroup of bsi_sort_select_kernel"""
+    return _slots_env("PILOSA_SORT_SLOTS", SORT_SLOTS_DEFAULT)
 
 
 # Extract(): set, time, mutex and bool fields through rows_extract_kernel (K28)
@@ -690,6 +683,35 @@ class GpuExecutor:
                 self._bsi_views[key] = rv
         return Leaf(rv, 0)
 
+    def _bsi_call(self, index: str, fname, c: Call, shards: List[int], max_depth: Optional[int] = None):
+        """The preamble of a filtered call on the int field ``fname``: (its BSI
+        group, the BSI view arena, the planned filter or None), or None where
+        the answer is empty without a launch -- no BSI view, or a filter known
+        empty from the schema.  NotImplementedError (the host answers) for a
+        field without a BSI group or deeper than ``max_depth``, more than one
+        child, or a filter the planner cannot take."""
+        f = self.holder.field(index, fname) if isinstance(fname, str) else None
+        b = f.bsi_group(fname) if f is not None else None
+        if b is None or len(c.children) > 1 or (max_depth is not None and b.bit_depth > max_depth):
+            raise NotImplementedError
+        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
+        if bv is None:
+            return None
+        filt = None
+        if c.children:
+            filt = self.plan(index, c.children[0], shards)
+            if filt is EMPTY:
+                return None
+        return b, bv, filt
+
+    @staticmethod
+    def _engine(fn, *args):
+        """an engine call whose CompileError leaves the call to the host"""
+        try:
+            return fn(*args)
+        except CompileError:
+            raise NotImplementedError
+
     def bsi_minmax(self, index: str, c: Call, shards: List[int], which: str):
         """Min/Max over the local shards -> ONE ValCount, folded vectorised
         exactly as the executor's per-shard reduce folds them in shard order
@@ -697,28 +719,16 @@ class GpuExecutor:
         with that shard's count: executor.go ValCount.Smaller).  Building and
         reducing ~1k per-shard objects in Python took most of the request."""
         from pilosa_amd.executor import ValCount
-        fname = c.args.get("field")
-        f = self.holder.field(index, fname) if isinstance(fname, str) else None
-        if f is None or f.bsi_group(fname) is None or len(c.children) > 1:
-            raise NotImplementedError
-        b = f.bsi_group(fname)
-        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
-        if bv is None:
+        call = self._bsi_call(index, c.args.get("field"), c, shards)
+        if call is None:
             return ValCount()
-        filt = None
-        if len(c.children) == 1:
-            filt = self.plan(index, c.children[0], shards)
-            if filt is EMPTY:
-                return ValCount()
+        b, bv, filt = call
         # per fragment (a wide one: all keys of its sub-shards, fragment.min/max
         # counts every column of the shard holding the value), then the first
         # fragment holding the extreme -- folded on the device, 3 int64 back
         sub = shardwidth.DEVICE_SUBSHARDS if shardwidth.WIDE else 1
-        try:
-            self.launches += 1
-            v, n, found = self.engine.bsi_minmax_folded(filt, bv, b.bit_depth, which, sub)
-        except CompileError:
-            raise NotImplementedError
+        self.launches += 1
+        v, n, found = self._engine(self.engine.bsi_minmax_folded, filt, bv, b.bit_depth, which, sub)
         if not found or n <= 0:
             return ValCount()
         return ValCount(v + b.base, n)
@@ -730,26 +740,13 @@ class GpuExecutor:
         bit is decided from the counts of all shards (bsi_kth_init, then one
         bsi_kth_step launch per bit; GpuEngine.bsi_kth)."""
         from pilosa_amd.executor import Executor, ValCount
-        fname = c.args.get("field")
-        f = self.holder.field(index, fname) if isinstance(fname, str) else None
-        if f is None or f.bsi_group(fname) is None or len(c.children) > 1:
-            raise NotImplementedError
+        call = self._bsi_call(index, c.args.get("field"), c, shards)
         nth = Executor.percentile_nth(c)
-        b = f.bsi_group(fname)
-        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
-        if bv is None:
-            self.percentile_device += 1   # no BSI view: answered here, without a launch
+        if call is None:
+            self.percentile_device += 1   # answered here, without a launch
             return ValCount()
-        filt = None
-        if len(c.children) == 1:
-            filt = self.plan(index, c.children[0], shards)
-            if filt is EMPTY:
-                self.percentile_device += 1   # a filter known empty from the schema: no launch either
-                return ValCount()
-        try:
-            r = self.engine.bsi_kth(filt, bv, b.bit_depth, nth.numerator, nth.denominator * 100)
-        except CompileError:
-            raise NotImplementedError
+        b, bv, filt = call
+        r = self._engine(self.engine.bsi_kth, filt, bv, b.bit_depth, nth.numerator, nth.denominator * 100)
         self.percentile_device += 1
         self.launches += 1   # bsi_kth_init
         if r is None:        # N == 0, read after init: no step ran
@@ -768,27 +765,12 @@ class GpuExecutor:
         clamped to what fits the LDS at the field's depth; default
         DISTINCT_SLOTS_DEFAULT)."""
         from pilosa_amd.executor import SignedRow
-        fname = c.args.get("field")
-        f = self.holder.field(index, fname) if isinstance(fname, str) else None
-        if f is None or f.bsi_group(fname) is None or len(c.children) > 1:
-            raise NotImplementedError
-        b = f.bsi_group(fname)
-        if b.bit_depth > distinct_max_depth():
-            raise NotImplementedError
-        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
-        if bv is None:
-            self.distinct_device += 1   # no BSI view: answered here, without a launch
+        call = self._bsi_call(index, c.args.get("field"), c, shards, distinct_max_depth())
+        if call is None:
+            self.distinct_device += 1   # answered here, without a launch
             return SignedRow()
-        filt = None
-        if len(c.children) == 1:
-            filt = self.plan(index, c.children[0], shards)
-            if filt is EMPTY:
-                self.distinct_device += 1   # a filter known empty from the schema: no launch either
-                return SignedRow()
-        try:
-            pos, neg = self.engine.bsi_distinct(filt, bv, b.bit_depth, distinct_slots_env())
-        except CompileError:
-            raise NotImplementedError
+        b, bv, filt = call
+        pos, neg = self._engine(self.engine.bsi_distinct, filt, bv, b.bit_depth, distinct_slots_env())
         self.distinct_device += 1
         self.launches += 1
         return SignedRow.from_values(np.concatenate([pos.astype(np.int64), -neg.astype(np.int64)]) + b.base)
@@ -862,23 +844,15 @@ class GpuExecutor:
         cannot take and a CompileError leave the map step to the host.
         PILOSA_SORT_SLOTS sets the tile slots per workgroup."""
         from pilosa_amd.executor import SortedColumns
-        if b is None or b.bit_depth > GpuEngine.SORT_MAX_PLANES or len(c.children) > 1:
+        if b is None:
             raise NotImplementedError
-        bv = self.view_arena(index, fname, VIEW_BSI_PREFIX + fname, shards)
-        if bv is None:
-            self.sort_device += 1   # no BSI view: answered here, without a launch
+        call = self._bsi_call(index, fname, c, shards, GpuEngine.SORT_MAX_PLANES)
+        if call is None:
+            self.sort_device += 1   # answered here, without a launch
             return SortedColumns()
-        filt = None
-        if len(c.children) == 1:
-            filt = self.plan(index, c.children[0], shards)
-            if filt is EMPTY:
-                self.sort_device += 1   # a filter known empty from the schema: no launch either
-                return SortedColumns()
-        try:
-            cols, vals, launches = self.engine.bsi_sort(filt, bv, b.bit_depth, b.base, window, desc, skip,
-                                                        sort_slots_env(), guard)
-        except CompileError:
-            raise NotImplementedError
+        _, bv, filt = call
+        cols, vals, launches = self._engine(self.engine.bsi_sort, filt, bv, b.bit_depth, b.base, window, desc, skip,
+                                            sort_slots_env(), guard)
         self.sort_device += 1
         self.launches += launches
         return SortedColumns(cols, vals)

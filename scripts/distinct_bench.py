@@ -140,7 +140,7 @@ def main():
         if filt_text:
             filt = gpu.plan("c", parse_string(filt_text).calls[0], shards)
             assert filt is not EMPTY
-        progs, ordered = eng._bsi_filter_program(filt, bv)
+        progs, ordered = eng._bsi_filter_program([filt], bv)
         targs = torch.from_numpy(eng.bsi_args(bv, DEPTH))
         tp, tv = eng.upload_batch(progs, ordered)
         words = (1 << DEPTH) >> 6

@@ -145,7 +145,7 @@ def main():
             out = {"filter": filt_text}
             filt = gpu.plan("c", parse_string(filt_text).calls[0], shards)
             assert filt is not EMPTY
-            progs, ordered = eng._bsi_filter_program(filt, bv)
+            progs, ordered = eng._bsi_filter_program([filt], bv)
             tp, tv = eng.upload_batch(progs, ordered)
             S = bv.S
             mode = 2 if bool(flat_mask(progs).all()) else 0

@@ -228,7 +228,7 @@ def main():
                 # ---- the steps alone: offsets as GpuEngine.bsi_extract computes them
                 filt = gpu.plan("c", parse_string(filt_text).calls[0], shards)
                 assert type(filt) is Leaf
-                progs, ordered = eng._bsi_filter_program(filt, view)
+                progs, ordered = eng._bsi_filter_program([filt], view)
                 tp, tv = eng.upload_batch(progs, ordered)
                 counts = torch.zeros(S * 16, dtype=torch.int32, device=eng.device)
                 eng.ext.expr_count(tp, tv, S, none64, counts, 2 if bool(flat_mask(progs).all()) else 0)
